@@ -3,7 +3,7 @@
 Poisson problem (BASELINE.json: "PCG iters/sec + T_solver, 8192x8192 grid at
 1/2/4/8 MI355X; L2 err vs analytic"), fp64, δ = 1e-6.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 8192]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--grid 8192] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -31,11 +31,23 @@ synchronise, before the closing CPU barrier: the ranks are coupled every
 iteration by the in-sweep sums, so the max over ranks is the job's time,
 without the gloo barrier's ~0.1-0.3 ms, which at 8 ranks would be ≈10 % of a
 20-step window).  `value` = job-wide PCG iterations/s (the grid is fixed →
-strong scaling).  Outside the timed region the script also runs one complete
-solve to convergence (w⁰ = 0: T_solver, iterations, L2 error against the
-analytic solution, timer breakdown incl. the cross-rank wait) and one with
-the BASELINE's random-init w⁰ (`random_init`; the reference has no random
-init, so its iteration count is parity-unpinned).
+strong scaling).  A plain run does only that: set up, warm up, time the K
+steps, print the JSON line.
+
+`--dump-outputs DIR` writes what the timed steps computed — the iterate w
+after the K-th step, this rank's block as the solver's caller receives it
+(`DeviceSolver.w()`) — as float64 `DIR/w.npy` (`DIR/w_rank<r>.npy` on N > 1
+GPUs).  A block beyond 32 MiB / N is written as a fixed, seeded sample of
+2²² / N of its nodes (the same nodes in every run of the same grid and
+decomposition, in ascending flat order).  The problem is analytic and the solve starts from
+w⁰ = 0, so the inputs are the same in every run with the same arguments.
+
+`--full` also runs, outside the timed region, one complete solve to
+convergence (w⁰ = 0: T_solver, iterations, L2 error against the analytic
+solution, timer breakdown incl. the cross-rank wait) and one with the
+BASELINE's random-init w⁰ (`random_init`; the reference has no random init,
+so its iteration count is parity-unpinned), and adds them to the JSON line;
+an unconverged solve makes the run invalid.
 
 Every multi-rank wait is bounded: PE_P2P_TIMEOUT_S (default 30 s here) on
 the in-sweep cross-rank sums, PE_WATCHDOG_S (default 60 s here) on every host
@@ -63,6 +75,10 @@ sys.path.insert(0, REPO)
 
 P100_ITERS_PER_S_8192 = 5889 / 270.0  # BASELINE.md §1b extrapolation (1× P100)
 
+DUMP_WHOLE_BYTES = 32 << 20  # --dump-outputs: a larger block is sampled
+DUMP_SAMPLE_NODES = 1 << 22  # 32 MiB of float64
+DUMP_SAMPLE_SEED = 8192
+
 
 def parse_args(argv):
     ap = argparse.ArgumentParser()
@@ -73,8 +89,13 @@ def parse_args(argv):
                     help="the warm-up lasts at least this long (GPU clocks ramp up under load; 0: exactly --warmup steps)")
     ap.add_argument("--grid", type=int, nargs="+", default=[8192, 8192])
     ap.add_argument("--decomp", default="device", help="device | aspect | reference | rows | cols | <Px>x<Py>")
-    ap.add_argument("--no-solve", action="store_true", help="skip the (untimed) full solves")
-    ap.add_argument("--no-random-solve", action="store_true", help="skip the (untimed) random-init solve")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the (untimed) full solves to convergence and report them in the JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the iterate w after the last timed step as float64 DIR/w.npy "
+                         "(a fixed seeded sample of a block beyond 32 MiB)")
+    ap.add_argument("--no-solve", action="store_true", help="with --full: skip the (untimed) full solves")
+    ap.add_argument("--no-random-solve", action="store_true", help="with --full: skip the (untimed) random-init solve")
     ap.add_argument("--seed", type=int, default=1234, help="random-init w0 seed")
     ap.add_argument("--variant", type=int, default=0)
     ap.add_argument("--algo", default="auto", choices=("auto", "classic", "fused", "two-step", "three-step"),
@@ -86,6 +107,23 @@ def parse_args(argv):
     ap.add_argument("--launch", default="eager", choices=("graph", "eager"),
                     help="timed steps launched eagerly (default) or replayed from instantiated hipGraphs")
     return ap.parse_args(argv)
+
+
+def dump_outputs(dirname: str, w, rank: int, world: int) -> str:
+    """Write this rank's block of the iterate (float64) under `dirname`; the
+    ranks share the 32 MiB equally."""
+    import numpy as np
+
+    w = np.ascontiguousarray(w, dtype=np.float64)
+    if w.nbytes > DUMP_WHOLE_BYTES // world:
+        idx = np.random.default_rng(DUMP_SAMPLE_SEED).integers(0, w.size, size=DUMP_SAMPLE_NODES // world,
+                                                               dtype=np.int64)
+        idx.sort()
+        w = w.reshape(-1)[idx]
+    os.makedirs(dirname, exist_ok=True)
+    path = os.path.join(dirname, "w.npy" if world == 1 else f"w_rank{rank}.npy")
+    np.save(path, w)
+    return path
 
 
 def _free_port() -> int:
@@ -290,8 +328,11 @@ def main(argv=None) -> int:
     st = solver.state()
     valid = int(st["status"]) == 0 and int(st["iter"]) == a.steps
 
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, solver.w(), rank, world)
+
     extra = {}
-    if not a.no_solve:
+    if a.full and not a.no_solve:
         # the full solve runs on the same solver (one construction, one
         # placement search; its T_solver still spans that construction)
         solver.set_check_tol(True)

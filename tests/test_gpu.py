@@ -250,7 +250,7 @@ def test_native_apps(gpu):
 
 def test_bench_contract(gpu):
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "50", "--warmup", "5", "--grid",
-                          "1024", "1024"], capture_output=True, text=True, check=True, timeout=300).stdout
+                          "1024", "1024", "--full"], capture_output=True, text=True, check=True, timeout=300).stdout
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
@@ -259,6 +259,59 @@ def test_bench_contract(gpu):
         assert k in d
     assert d["steps"] == 50 and d["n_gpus"] == 1 and d["valid"] and d["value"] > 0
     assert d["converged"] and d["l2_err"] < 1e-3
+
+
+def _bench_dump(tmp_path, name, M, N, steps):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                          "--warmup", "3", "--warmup-s", "0", "--grid", str(M), str(N), "--dump-outputs",
+                          str(tmp_path / name)], capture_output=True, text=True, check=True, timeout=300).stdout
+    lines = [l for l in out.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0]), np.load(tmp_path / name / "w.npy")
+
+
+def test_bench_plain_run_dumps_outputs(gpu, tmp_path):
+    """A plain run times its steps only (no solve in its JSON line) and
+    --dump-outputs writes the iterate after the last timed step: 10 steps of
+    the resident kernel from w⁰ = 0 against the fp64 recurrence, the same
+    array from a second run."""
+    from poisson_ellipse_openmp_mpi_cuda_amd.ops import torch_ref
+
+    M, N, K = 40, 40, 10
+    d, w = _bench_dump(tmp_path, "a", M, N, K)
+    assert d["valid"] and d["steps"] == K and d["dtype"] == "fp64" and d["higher_is_better"] is True
+    assert d["ms_per_step"] == pytest.approx(1000.0 / d["value"], rel=1e-9)
+    for k in ("converged", "iters_converged", "l2_err", "t_solver_s", "random_init"):
+        assert k not in d
+    assert w.dtype == np.float64 and w.shape == (M - 1, N - 1)
+    wref = torch_ref.single_sweep(EllipseProblem(M, N), K).w[1:M, 1:N].numpy()
+    assert np.abs(w - wref).max() <= 1e-12 * np.abs(wref).max()
+    _, w2 = _bench_dump(tmp_path, "b", M, N, K)
+    assert np.abs(w2 - wref).max() <= 1e-12 * np.abs(wref).max()
+
+
+def test_bench_dump_outputs_samples_large_block(gpu, tmp_path):
+    """A block beyond 32 MiB (2100×2100 nodes) is dumped as the fixed seeded
+    sample: 2²² of its nodes in ascending flat order, the values of the
+    solver's own 6 steps at those nodes."""
+    import bench
+
+    M = N = 2101
+    K = 6
+    d, w = _bench_dump(tmp_path, "s", M, N, K)
+    assert d["valid"] and d["steps"] == K
+    assert w.dtype == np.float64 and w.shape == (bench.DUMP_SAMPLE_NODES,) and w.nbytes <= 64 << 20
+    idx = np.random.default_rng(bench.DUMP_SAMPLE_SEED).integers(0, (M - 1) * (N - 1), size=bench.DUMP_SAMPLE_NODES,
+                                                                 dtype=np.int64)
+    idx.sort()
+    opt = gpu.SolveOptions()
+    opt.check_tol = False
+    s = gpu.DeviceSolver(EllipseProblem(M, N).to_native(), D.block(M, N, 1, 0), None, opt)
+    s.reset()
+    s.run_iterations(K, False)
+    s.synchronize()
+    full = s.w().reshape(-1)
+    assert np.abs(w - full[idx]).max() <= 1e-12 * np.abs(full).max()
 
 
 @pytest.mark.parametrize("warmup", ["0", "5"])
@@ -297,7 +350,7 @@ def test_two_process_device_path_host_staged(gpu):
     assert d["l2_err"] == pytest.approx(3.06e-4, rel=5e-3)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps",
-           "30", "--warmup", "3", "--grid", "512", "512"]
+           "30", "--warmup", "3", "--grid", "512", "512", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -563,7 +616,7 @@ def test_bench_halo_push_graphs(gpu, nproc, halo):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", str(nproc), "--steps", "40", "--warmup", "4", "--grid", str(M), str(N), "--decomp", "rows",
-           "--launch", "graph"]
+           "--launch", "graph", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -589,7 +642,7 @@ def test_bench_reports_transport_fallbacks(gpu, fault):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3",
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "3", "--steps", "12", "--warmup", "3", "--grid", "400", "600", "--decomp", "rows",
-           "--no-random-solve"]
+           "--full", "--no-random-solve"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
@@ -618,7 +671,7 @@ def test_bench_self_launch_and_random_init(gpu):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20",
-                          "--warmup", "2", "--grid", "512", "512", "--decomp", "rows"], cwd=ROOT, env=env,
+                          "--warmup", "2", "--grid", "512", "512", "--decomp", "rows", "--full"], cwd=ROOT, env=env,
                          capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

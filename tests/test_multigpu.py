@@ -143,7 +143,7 @@ def test_bench_multi_gpu_contract(gpu, nproc):
     env.pop("PE_COMM", None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
            "--master-addr", "127.0.0.1", "--master-port", str(free_port()), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(nproc), "--steps", "40", "--warmup", "5", "--grid", "2048", "2048"]
+           "--gpus", str(nproc), "--steps", "40", "--warmup", "5", "--grid", "2048", "2048", "--full"]
     out = _run(cmd, env, timeout=300)
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -173,7 +173,7 @@ def test_bench_self_launch_real_gpus(gpu, nproc):
     for k in ("PE_COMM", "WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
     out = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "40", "--warmup",
-                "5", "--grid", "2048", "2048", "--no-random-solve"], env, timeout=300)
+                "5", "--grid", "2048", "2048", "--full", "--no-random-solve"], env, timeout=300)
     lines = [l for l in out.splitlines() if l.startswith("{")]
     assert len(lines) == 1
     d = json.loads(lines[0])
