@@ -1,6 +1,6 @@
 # Build for MI355X (gfx950).  Host C++ with g++ (OpenMP via libgomp, the same
 # runtime PyTorch ships), device code with hipcc --offload-arch=gfx950.
-#   make            → python extension + CLI apps (bin/pe_hip, bin/pe_cpu, bin/pe_launch)
+#   make            → python extension + CLI apps (bin/pe_hip, bin/pe_cpu, bin/pe_launch, bin/pe_layout)
 #   make cpu        → CPU-only pieces
 #   make clean
 ROCM      ?= /opt/rocm
@@ -25,8 +25,8 @@ HIPFLAGS  += $(COMMON) --offload-arch=$(ARCH) -ffp-contract=off -mcode-object-ve
              -fno-gpu-rdc -munsafe-fp-atomics
 LDLIBS    := -L$(ROCM)/lib -lamdhip64 -lrccl -lrocprofiler-sdk-roctx -lgomp -lpthread -Wl,-rpath,$(ROCM)/lib
 
-CORE_SRC  := csrc/core/decomp.cpp csrc/core/thread_comm.cpp csrc/core/report.cpp csrc/cpu/pcg_cpu.cpp
-HOST_SRC  := csrc/hip/device_solver.cpp csrc/hip/item_layout.cpp csrc/hip/placement.cpp csrc/hip/checkpoint.cpp csrc/hip/halo_path.cpp csrc/hip/rccl_comm.cpp csrc/hip/p2p_comm.cpp csrc/hip/runtime.cpp csrc/core/row_classes.cpp
+CORE_SRC  := csrc/core/decomp.cpp csrc/core/thread_comm.cpp csrc/core/report.cpp csrc/core/item_layout.cpp csrc/core/row_classes.cpp csrc/cpu/pcg_cpu.cpp
+HOST_SRC  := csrc/hip/device_solver.cpp csrc/hip/item_layout.cpp csrc/hip/placement.cpp csrc/hip/checkpoint.cpp csrc/hip/halo_path.cpp csrc/hip/rccl_comm.cpp csrc/hip/p2p_comm.cpp csrc/hip/runtime.cpp
 HIP_SRC   := csrc/hip/kernels.hip csrc/hip/fused.hip csrc/hip/fused2.hip csrc/hip/fused3.hip csrc/hip/resident.hip csrc/hip/p2p.hip
 BIND_SRC  := csrc/bind/module.cpp
 
@@ -39,7 +39,7 @@ HEADERS   := $(wildcard csrc/include/pe/*.hpp) $(wildcard csrc/hip/*.hpp) csrc/a
 EXT       := $(PKG)/_native$(EXT_SUF)
 
 .PHONY: all cpu clean asan tsan
-all: $(EXT) $(BIN)/pe_hip $(BIN)/pe_cpu $(BIN)/pe_launch
+all: $(EXT) $(BIN)/pe_hip $(BIN)/pe_cpu $(BIN)/pe_launch $(BIN)/pe_layout
 cpu: $(BIN)/pe_cpu
 
 $(BUILD)/%.o: csrc/%.cpp $(HEADERS)
@@ -65,6 +65,10 @@ $(BIN)/pe_hip: $(BUILD)/apps/pe_hip.o $(CORE_OBJ) $(HOST_OBJ) $(HIP_OBJ)
 	@mkdir -p $(BIN)
 	$(CXX) -o $@ $^ $(LDLIBS)
 
+$(BIN)/pe_layout: $(BUILD)/apps/pe_layout.o $(BUILD)/core/item_layout.o $(BUILD)/core/row_classes.o $(BUILD)/core/decomp.o
+	@mkdir -p $(BIN)
+	$(CXX) -o $@ $^
+
 $(BIN)/pe_launch: $(BUILD)/apps/pe_launch.o
 	@mkdir -p $(BIN)
 	$(CXX) -o $@ $^ -lpthread
@@ -73,7 +77,13 @@ $(BIN)/pe_launch: $(BUILD)/apps/pe_launch.o
 # ASan / XNACK): AddressSanitizer + UBSan, and ThreadSanitizer for the
 # thread-rank transport (run with --threads 1: libgomp is not TSan-built).
 SAN_SRC   := $(CORE_SRC) csrc/apps/pe_cpu.cpp
-asan: $(BIN)/pe_cpu_asan
+# (the layout planner: host arithmetic over prefix arrays; links no HIP)
+LAY_SRC   := csrc/core/item_layout.cpp csrc/core/row_classes.cpp csrc/core/decomp.cpp csrc/apps/pe_layout.cpp
+asan: $(BIN)/pe_cpu_asan $(BIN)/pe_layout_asan
+$(BIN)/pe_layout_asan: $(LAY_SRC) $(HEADERS)
+	@mkdir -p $(BIN)
+	$(CXX) -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -Icsrc/include -fno-omit-frame-pointer \
+	  -fsanitize=address,undefined -fno-sanitize-recover=undefined $(LAY_SRC) -o $@
 tsan: $(BIN)/pe_cpu_tsan
 $(BIN)/pe_cpu_asan: $(SAN_SRC) $(HEADERS)
 	@mkdir -p $(BIN)

@@ -36,6 +36,13 @@ py::dict timers_dict(const Timers& t) {
   return d;
 }
 
+// (first row, rows, strip, flags: kBandBit | kUniBit) per list position; rows 0: an empty position
+std::vector<std::tuple<int, int, int, int>> entry_tuples(const std::vector<Entry>& list) {
+  std::vector<std::tuple<int, int, int, int>> v;
+  for (const Entry& e : list) v.emplace_back(e.x & dev::kRowMask3, e.y >> 20, e.y & 0xFFFFF, e.x & ~dev::kRowMask3);
+  return v;
+}
+
 py::array_t<double> to_array(std::vector<double>&& v, int64_t rows, int64_t cols) {
   auto* heap = new std::vector<double>(std::move(v));
   py::capsule owner(heap, [](void* p) { delete static_cast<std::vector<double>*>(p); });
@@ -281,6 +288,72 @@ PYBIND11_MODULE(_native, m) {
     return py::make_tuple(to_array(std::move(a), R, C), to_array(std::move(b), R, C), ca);
   });
 
+  // ---- item layouts (host only: no device needed) -----------------------
+  m.def(
+      "sweep_geometry",
+      [](int64_t nx, int64_t ny, int steps) {
+        const SweepGeometry g = sweep_geometry(nx, ny, steps, true);
+        py::dict d;
+        d["fsw"] = g.fsw;
+        d["hdep"] = g.hdep;
+        d["xorg"] = g.xorg;
+        d["strips"] = g.strips;
+        d["plane"] = g.plane;
+        d["rows_hi"] = g.rows_hi;
+        d["cols_hi"] = g.cols_hi;
+        d["tab_lo"] = g.tab_lo;
+        d["xsize"] = g.xsize;
+        d["wsize"] = g.wsize;
+        return d;
+      },
+      py::arg("nx"), py::arg("ny"), py::arg("steps"), "field planes, strips and table ranges of a block's sweep");
+  m.def(
+      "ti_candidates",
+      [](int64_t nx, int64_t ny, int steps, int wave_cap) {
+        return ti_candidates(sweep_geometry(nx, ny, steps, true), nx, ny, wave_cap);
+      },
+      py::arg("nx"), py::arg("ny"), py::arg("steps"), py::arg("wave_cap") = 2048,
+      "rows-per-item candidates of the construction's tuning");
+  m.def(
+      "item_layout",
+      [](const Problem& P, const Block& blk, int steps, int ti, int order, bool overlap, const std::string& layout,
+         std::pair<int, int> wave_caps, int cus, int ov_reserve, double young, int wperm, int ov_debug,
+         const std::string& force_layout) {
+        LayoutRequest q;
+        q.ti = ti;
+        q.order = order;
+        q.overlap = overlap;
+        q.name = layout;
+        q.wave_caps[0] = wave_caps.first;
+        q.wave_caps[1] = wave_caps.second;
+        q.wave_cap = std::min(wave_caps.first, wave_caps.second);
+        q.cus = cus;
+        q.ov_reserve = ov_reserve;
+        q.knobs.young = young;
+        q.knobs.wperm = wperm;
+        q.knobs.ov_debug = ov_debug;
+        q.knobs.force_layout = force_layout;
+        const ItemLayout l = block_planner(P, blk, steps).build(q);
+        py::dict d;
+        d["entries"] = entry_tuples(l.list);
+        d["boundary"] = l.lnb[0];
+        d["shards"] = l.lnsh;
+        d["lbase"] = std::vector<int>(l.lbase, l.lbase + 9);
+        d["lnb"] = std::vector<int>(l.lnb, l.lnb + 8);
+        d["waves"] = l.lwaves;
+        d["name"] = l.name;
+        d["cuts"] = l.cuts;
+        d["load"] = std::vector<double>{l.max, l.mean, double(l.items)};
+        d["nblocks"] = l.nblocks;
+        d["nslots"] = l.nslots;
+        return d;
+      },
+      py::arg("prob"), py::arg("block"), py::arg("steps"), py::arg("ti"), py::arg("order") = 0,
+      py::arg("overlap") = false, py::arg("layout") = "lpt", py::arg("wave_caps") = std::make_pair(2048, 2048),
+      py::arg("cus") = 256, py::arg("ov_reserve") = 8, py::arg("young") = 1.0, py::arg("wperm") = 0,
+      py::arg("ov_debug") = 0, py::arg("force_layout") = "",
+      "the item list a solver of this block would walk (the defaults: two 4-wave workgroups on each of 256 CUs)");
+
   // ---- device (HIP / RCCL) ----------------------------------------------
   m.def("device_count", &device_count);
   m.def("set_device", &set_device);
@@ -457,12 +530,31 @@ PYBIND11_MODULE(_native, m) {
           "layout_entries",
           [](const DeviceSolver& s) {
             // (first row, rows, strip, flags) per list position; rows 0: an empty position
-            std::vector<std::tuple<int, int, int, int>> v;
-            for (const int2& e : s.layout_entries())
-              v.emplace_back(e.x & dev::kRowMask3, e.y >> 20, e.y & 0xFFFFF, e.x & ~dev::kRowMask3);
-            return v;
+            return entry_tuples(s.layout_entries());
           },
           "the static item list: (first row, rows, strip, flags: kBandBit | kUniBit)")
+      .def_property_readonly(
+          "layout_request",
+          [](const DeviceSolver& s) {
+            const LayoutRequest& q = s.layout_request();
+            py::dict d;
+            d["prob"] = s.problem();
+            d["block"] = s.block();
+            d["steps"] = s.sweep_steps();
+            d["ti"] = q.ti;
+            d["order"] = q.order;
+            d["overlap"] = q.overlap;
+            d["layout"] = q.name;
+            d["wave_caps"] = py::make_tuple(q.wave_caps[0], q.wave_caps[1]);
+            d["cus"] = q.cus;
+            d["ov_reserve"] = q.ov_reserve;
+            d["young"] = q.knobs.young;
+            d["wperm"] = q.knobs.wperm;
+            d["ov_debug"] = q.knobs.ov_debug;
+            d["force_layout"] = q.knobs.force_layout;
+            return d;
+          },
+          "what the solver last asked the layout planner: the keyword arguments of item_layout()")
       .def_property_readonly("layout_waves", [](DeviceSolver& s) { return s.params().lwaves; })
       .def_property_readonly("strips", [](DeviceSolver& s) { return s.params().nstrips; }, "wave strips across the block")
       .def_property_readonly("layout_boundary", &DeviceSolver::layout_boundary,

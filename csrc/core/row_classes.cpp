@@ -18,7 +18,7 @@
 #include <climits>
 #include <vector>
 
-#include "pe/device.hpp"
+#include "pe/row_classes.hpp"
 
 namespace pe {
 namespace {
@@ -170,6 +170,14 @@ void host_coefficients(const Problem& P, const Block& blk, std::vector<double>& 
         cls[at] = 2;
       }
     }
+}
+
+LayoutPlanner block_planner(const Problem& P, const Block& blk, int steps, bool fused) {
+  const SweepGeometry g = sweep_geometry(blk.nx, blk.ny, steps, fused);
+  const std::vector<double> t = chord_tables(P, blk, g.rows_hi, g.cols_hi, g.tab_lo);
+  const double* row = t.data() + (g.rows_hi - g.tab_lo + 1) * 4;
+  const bool has[4] = {blk.has(LEFT), blk.has(RIGHT), blk.has(DOWN), blk.has(UP)};
+  return LayoutPlanner(g, blk.nx, blk.ny, has, row_classes(t.data(), row, g.rows_hi, g.cols_hi, g.tab_lo));
 }
 
 }  // namespace pe

@@ -48,7 +48,7 @@ void DeviceSolver::save_checkpoint(const std::string& path) {
   PE_HIP_CHECK(hipStreamSynchronize(stream_));
   std::vector<std::pair<void*, size_t>> bufs;
   if (fused_) {
-    bufs = {{fields_, sizeof(double) * xsize_}, {xalt_, sizeof(double) * xsize_}, {walt_, sizeof(double) * wsize_}};
+    bufs = {{fields_, sizeof(double) * geo_.xsize}, {xalt_, sizeof(double) * geo_.xsize}, {walt_, sizeof(double) * geo_.wsize}};
   } else {
     bufs = {{fields_, sizeof(double) * 4 * blk_.alloc}};
   }
@@ -97,7 +97,7 @@ void DeviceSolver::load_checkpoint(const std::string& path) {
   if (!f) throw std::runtime_error("resume: cannot open " + path);
   CkptHeader h{};
   ck_io(f, &h, sizeof(h), false, path);
-  size_t field_bytes = fused_ ? sizeof(double) * (2 * xsize_ + wsize_) : sizeof(double) * 4 * blk_.alloc;
+  size_t field_bytes = fused_ ? sizeof(double) * (2 * geo_.xsize + geo_.wsize) : sizeof(double) * 4 * blk_.alloc;
   const bool ok = std::memcmp(h.magic, "PECKPT1", 8) == 0 && h.version == 1 && h.M == prob_.M && h.N == prob_.N &&
                   h.rank == blk_.rank && h.Px == blk_.Px && h.Py == blk_.Py && h.fused == (sstep_ ? steps_ : fused_ ? 1 : 0) &&
                   h.variant == opt_.variant && h.i0 == blk_.i0 && h.j0 == blk_.j0 && h.nx == blk_.nx &&
@@ -129,9 +129,9 @@ void DeviceSolver::load_checkpoint(const std::string& path) {
   };
   load(st_, sizeof(DevState));
   if (fused_) {
-    load(fields_, sizeof(double) * xsize_);
-    load(xalt_, sizeof(double) * xsize_);
-    load(walt_, sizeof(double) * wsize_);
+    load(fields_, sizeof(double) * geo_.xsize);
+    load(xalt_, sizeof(double) * geo_.xsize);
+    load(walt_, sizeof(double) * geo_.wsize);
   } else {
     load(fields_, sizeof(double) * 4 * blk_.alloc);
   }

@@ -20,9 +20,6 @@
 #include <cstddef>
 #include <cstring>
 #include <deque>
-#include <map>
-#include <mutex>
-#include <queue>
 #include <limits>
 #include <thread>
 
@@ -217,46 +214,19 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
   if (const char* e = std::getenv("PE_TI")) ti_env = std::atoi(e);
   if (ti_env > 0) ti = ti_env;
 
-  int64_t strips = 0, rows_hi = nx + 2, cols_hi = ny + 2;
+  geo_ = sweep_geometry(nx, ny, steps_, fused_);
+  const int64_t strips = geo_.strips, rows_hi = geo_.rows_hi, cols_hi = geo_.cols_hi;
   if (fused_) {
-    // Planes: columns -1 .. 124·nstrips+2 (strip loads never leave the row),
-    // rows -1 .. nx+4 (two prefetch rows past the halo).  x[b] interleaves the
-    // r and p planes by row.  Two-step sweep: halo depth 4 — columns -3 ..
-    // 120·nstrips+4, rows -3 .. nx+6.
-    fsw_ = steps_ >= 3 ? dev::kFSW3 : steps_ == 2 ? dev::kFSW2 : dev::kFSW;
-    hdep_ = 2 * steps_;
-    xorg_ = steps_ >= 3 ? dev::kHL3 - 1 : hdep_ - 1;
-    strips = (ny + fsw_ - 1) / fsw_;
-    plane_ = ((fsw_ * strips + 2 * hdep_ + 7) / 8) * 8;
-    // Three-step: strip s loads columns 48s-7 .. 48s+56 (one per lane) and
-    // outputs 48s+1 .. 48s+48.  Element 0 of a row is column -7 and the
-    // plane a whole number of 128-B lines, so every strip's loads are 4 whole
-    // lines and its stores 6 whole 64-B segments of r, p and w (52 outputs of
-    // 64 loaded straddled 64-B segments: partial writes from two strips, and
-    // 5 lines touched for 4 lines of data).
-    if (steps_ >= 3) plane_ = ((xorg_ + fsw_ * (strips - 1) + 64 - dev::kHL3 + 1 + 15) / 16) * 16;
-    const int64_t rows = nx + 2 * hdep_ + 2;
-    xsize_ = ((rows * 2 * plane_ + 64 + 31) / 32) * 32;
-    wsize_ = ((rows * plane_ + 64 + 31) / 32) * 32;
-    k.pitch = 2 * plane_;
-    k.wpitch = plane_;
-    k.poff = plane_;
-    fields_ = static_cast<double*>(field_alloc(sizeof(double) * xsize_));
-    xalt_ = static_cast<double*>(field_alloc(sizeof(double) * xsize_));
-    walt_ = static_cast<double*>(field_alloc(sizeof(double) * wsize_));
+    k.pitch = 2 * geo_.plane;
+    k.wpitch = geo_.plane;
+    k.poff = geo_.plane;
+    fields_ = static_cast<double*>(field_alloc(sizeof(double) * geo_.xsize));
+    xalt_ = static_cast<double*>(field_alloc(sizeof(double) * geo_.xsize));
+    walt_ = static_cast<double*>(field_alloc(sizeof(double) * geo_.wsize));
     mark("field allocs");
     set_fused_fields(fields_, xalt_, walt_);
-    hsize_ = std::max<int64_t>(1, nx) * 2 * hdep_;  // y strips: hdep columns of r and p per owned row
-    // (multi-step: rows -hdep .. nx+hdep+2, columns -hdep .. fsw·strips+hdep+3)
-    rows_hi = sstep_ ? nx + hdep_ + 2 : nx + 3;
-    cols_hi = sstep_ ? fsw_ * strips + hdep_ + 3 : dev::kFSW * strips + 3;
-    tab_lo_ = sstep_ ? -hdep_ : -1;
-    if (steps_ >= 3) {  // the last strip's last lane + 3; the first strip's lane 0 is column -xorg
-      cols_hi = fsw_ * (strips - 1) + 64 - dev::kHL3 + 3;
-      tab_lo_ = -(xorg_ + 1);
-    }
+    hsize_ = std::max<int64_t>(1, nx) * 2 * geo_.hdep;  // y strips: hdep columns of r and p per owned row
   } else {
-    strips = (ny + dev::kSW - 1) / dev::kSW;
     const int64_t A = blk_.alloc;
     PE_HIP_CHECK(hipMalloc(&fields_, sizeof(double) * A * 4));
     k.pitch = blk_.pitch;
@@ -268,7 +238,7 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
     hsize_ = std::max<int64_t>(1, nx);
   }
   mark("fields");
-  const int64_t nrow_tab = rows_hi - tab_lo_ + 1, ncol_tab = cols_hi - tab_lo_ + 1;
+  const int64_t nrow_tab = rows_hi - geo_.tab_lo + 1, ncol_tab = cols_hi - geo_.tab_lo + 1;
   const int64_t ntab = nrow_tab * 4 + ncol_tab * 4;
   PE_HIP_CHECK(hipMalloc(&tables_, sizeof(double) * ntab));
   PE_HIP_CHECK(hipMalloc(&rowcls_, sizeof(int) * nrow_tab * 4));
@@ -284,7 +254,7 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
 
   k.fused = fused_ ? 1 : 0;
   k.steps = steps_;
-  k.hdep = hdep_;
+  k.hdep = geo_.hdep;
   k.pre_load = 1;  // first item's list entry + row classes loaded at kernel entry (fused3.hip Pre3)
   k.dring = 1;     // band rows read 1/D from the LDS ring (+0.7 % at 8192², profiles/r5_ab_kernel.txt)
   // SIMD priority turns (fused3.hip prio_turn), opt-in: 1-GPU 2048² and
@@ -293,7 +263,7 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
   // it/s, the 8-rank slab and 4×2 blocks neutral — profiles/r5_prio.txt
   k.prio = std::getenv("PE_PRIO") ? std::max(0, std::min(20, std::atoi(std::getenv("PE_PRIO")))) : 0;
   k.stage = !(std::getenv("PE_STAGE") && std::atoi(std::getenv("PE_STAGE")) == 0);
-  k.xorg = xorg_;
+  k.xorg = geo_.xorg;
   k.nx = nx;
   k.ny = ny;
   k.M = prob_.M;
@@ -318,10 +288,10 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
   k.weighted = prob_.norm == Norm::Weighted ? 1 : 0;
   k.max_iter = prob_.iter_cap();
   for (int d = 0; d < 4; ++d) k.has[d] = blk_.has(d) ? 1 : 0;
-  // tables start at local index tab_lo_; the kernels index them by (local + 1)
-  k.colT = tables_ - (tab_lo_ + 1) * 4;
-  k.rowcls = rowcls_ - (tab_lo_ + 1) * 4;
-  k.rowT = tables_ + nrow_tab * 4 - (tab_lo_ + 1) * 4;
+  // tables start at local index geo_.tab_lo; the kernels index them by (local + 1)
+  k.colT = tables_ - (geo_.tab_lo + 1) * 4;
+  k.rowcls = rowcls_ - (geo_.tab_lo + 1) * 4;
+  k.rowT = tables_ + nrow_tab * 4 - (geo_.tab_lo + 1) * 4;
   k.send_dn = halo_;
   k.send_up = halo_ + hsize_;
   k.recv_dn = halo_ + 2 * hsize_;
@@ -425,31 +395,11 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
     const int per0 = dev::resident_blocks_S(k, 0);
     if (per0 > 0) wave_cap0 = cus * per0 * dev::kWPB;
   }
-  wave_cap_ = std::min(wave_cap, wave_cap0);
   wave_caps_[0] = wave_cap;
   wave_caps_[1] = wave_cap0;
   // Rows per item: fixed (PE_TI, the classic path, blocks ≥ 2²⁴ nodes), or
-  // tuned below among kTiCands for smaller static single sweeps (the best depends
-  // on the block: 2400×3200 18 rows 76 µs vs 84 at 10; 1600×2400 and the
-  // 8-rank 8192² block 10 rows — profiles/r2_mid_tune.txt).
-  static constexpr int kTiCands[4] = {8, 10, 14, 18};
+  // tuned among ti_candidates() for smaller static sweeps.
   tune_ti_ = fused_ && ti_env == 0 && k.order == 0 && npts >= double(1 << 20) && !big;
-  // Two-step sweep: tuned among {16, 24, 32, 40, 48} below 2²⁵ nodes (the
-  // best height moves with the block: 1600×2400 16 rows 39.9 µs/iter vs 47.7
-  // at 40, 2048² 24 rows, 4096² 32 rows 102.3 vs 108.7; 8192² and 16384²
-  // within ±2 % over 24-48 rows: fixed 40 — one placement per grid,
-  // tools/ti_probe.py, profiles/r3_ti_probe.txt).  Three-step sweep (12
-  // pipeline-fill rows per item): among {32 .. 96} (2400×3200 32 rows 45.7
-  // µs/iter vs 57.1 at 64, 1600×2400 and 2048² 48, 4096² 64); fixed above,
-  // with the aligned 48-column strips: 8192² 112 rows (240-247 µs/iter vs
-  // 253-256 at 80, 266-271 at 104, 249 at 120, 255 at 128 — the same on two
-  // boxes and with padded rows; a scan of 64-224 found only 132 as good),
-  // 16384² 448 (867 vs 880 at 272, 891-899 at 256, 975 at 288, 934-940 at
-  // 512; 256 was 939 vs 959 at 128 on another box) — tools/layout_probe.py,
-  // tools/block_probe.py, profiles/r4_ti48.txt.
-  static constexpr int kTiCands2[5] = {16, 24, 32, 40, 48};
-  static constexpr int kTiCands3[5] = {32, 48, 64, 80, 96};
-  const int* tic = steps_ >= 3 ? kTiCands3 : kTiCands2;
   // (from 2²⁰ nodes: a tuned layout depends on the timings, so two
   // constructions of a smaller block — a checkpointed solve and its resume —
   // could lay it out differently and the resume would not be bitwise; round 5
@@ -464,39 +414,13 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
   // other two at their best rows per item.
   if (steps_ >= 3) lay_name_ = npts >= 5e7 ? "lpt" : npts >= 2.5e7 ? "fill" : "equal";
   if (const char* e = std::getenv("PE_TI_TUNE")) tune_ti_ = tune_ti_ && std::atoi(e) != 0;
-  // Tuning candidates: the fixed set plus, for q = 1..5 items per wave, the
-  // smallest item height that gives every wave at most q items — a static
-  // layout's sweep lasts as long as its most loaded wave, and 3.4 items per
-  // wave means a quarter of the waves runs a 4th item while the rest idle
-  // (8-rank 8192² block at 10 rows: busy fraction 0.74-0.78,
-  // tools/stamp_probe.py).  (Round 5 measured one short item per wave — down
-  // to 4 rows — on the 2-rank blocks of 1600×2400 and 2048²: 86.9-88.2 µs per
-  // sweep against 58.9-64 at 32-96 rows; the 12 pipeline-fill rows of a short
-  // item cost more than the waves it adds — profiles/r5_ab_layout.txt.)
   std::vector<int> ti_cands;
-  if (tune_ti_) {
-    ti_cands.assign(kTiCands, kTiCands + 4);
-    if (sstep_) ti_cands.assign(tic, tic + 5);
-    // taller items for the largest tuned blocks (4096²: 30 rows 158 µs vs 165
-    // at 18, one placement, profiles/r2_ti_big.txt)
-    if (npts >= 12e6 && !sstep_) ti_cands.insert(ti_cands.end(), {24, 30});
-    const int64_t W = std::max(dev::kWPB, wave_cap_);
-    const int tlo = sstep_ ? tic[0] : kTiCands[0], thi = steps_ >= 3 ? 128 : sstep_ ? dev::kTImax2 : 40;
-    for (int q = 2; q <= 5; ++q)
-      for (int t = tlo; t <= thi; ++t)
-        if (int64_t(strips) * ((nx + t - 1) / t) <= int64_t(q) * W) {
-          ti_cands.push_back(t);
-          break;
-        }
-    std::sort(ti_cands.begin(), ti_cands.end());
-    ti_cands.erase(std::unique(ti_cands.begin(), ti_cands.end()), ti_cands.end());
-  }
+  if (tune_ti_) ti_cands = ti_candidates(geo_, nx, ny, std::min(wave_cap, wave_cap0));
   const int ti_min = tune_ti_ ? ti_cands.front() : ti;
-  set_items(ti);
   // block partials: interior grid, then (overlap) the boundary grid after it
   const int64_t npart = 8 * std::max<int64_t>(2 * int64_t(std::max(wave_cap, wave_cap0) / dev::kWPB + 1), 4096);
-  // item-sum slots: one per item, more when setup_items splits tail items
-  // (static sweeps split heavy items into up to ti pieces: setup_items)
+  // item-sum slots: one per item (static sweeps split heavy items into up to
+  // ti pieces: the planner)
   const int64_t nitems_max = strips * ((nx + ti_min - 1) / ti_min);
   nslot_cap_ = fused_ ? int((k.order == 0 ? ti + 1 : 2) * nitems_max + 64) : 0;
   PE_HIP_CHECK(hipMalloc(&partial_, sizeof(double) * (npart + 8 * int64_t(nslot_cap_))));
@@ -510,154 +434,25 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
   k.dinv_out = 1.0 / ((k.inv_eps + k.inv_eps) * k.ih1sq + (k.inv_eps + k.inv_eps) * k.ih2sq);
   mark("buffers");
   build_tables(rows_hi, cols_hi);
+  const bool has[4] = {blk_.has(LEFT), blk_.has(RIGHT), blk_.has(DOWN), blk_.has(UP)};
+  planner_ = std::make_unique<LayoutPlanner>(geo_, nx, ny, has, rowcls_host_);
   mark("tables");
   if (const char* e = std::getenv("PE_P2P_TIMEOUT_S")) put_timeout_s_ = std::max(0.1, std::atof(e));
   setup_halo_push();
   setup_halo_put();
   // The placement search times the item layout the solve will run (after
-  // setup_items): its best class then reaches the early-stop rate (8192²
+  // apply_layout): its best class then reaches the early-stop rate (8192²
   // static layout 0.536-0.545 ms vs 0.564-0.567 for the plain walk), so it
   // stops after 2-3 tries instead of 8 — construction 0.10-0.14 vs 0.15-0.25 s,
   // the same iteration speed (profiles/r2_bench_psearch.txt).
   if (comm_->size() > 1) measure_exchange();  // (diagnostic: the comm's exchange, bench JSON)
-  setup_items();
+  apply_layout(ti);
   mark("items");
   if (fused_) choose_placement();
   mark("placement");
   setup_resident();
   mark("resident");
-  if (tune_ti_ && !resident_) {
-    // time S_0 + 1 + 4 local sweeps per candidate on real data (no
-    // communication: the in-sweep cross-rank sum is not set up yet) and keep
-    // the fastest; every rank tunes its own block
-    Range range("pe.tune_rows_per_item");
-    // candidates: the fixed set plus, for q = 2..5 items per wave, the
-    // smallest item height that gives every wave at most q items — a static
-    // layout's sweep lasts as long as its most loaded wave, and 3.4 items per
-    // wave means a quarter of the waves runs a 4th item while the rest idle
-    // (8-rank 8192² block at 10 rows: busy fraction 0.74-0.78, tools/stamp_probe.py)
-    // (candidates: ti_cands above)
-    std::vector<int> cands = ti_cands;
-    float best_ms = 0.f;
-    int best = ti;
-    // one candidate: S_0 + 1 + kTimed local sweeps on real data, the last
-    // kTimed timed (round 3: S_0 + 2 + 6 — construction is inside T_solver)
-    constexpr int kTimed = 4;
-    // Trials run pipelined: the host lays out trial i+1 while the GPU times
-    // trial i (the list upload is stream-ordered after those sweeps), and
-    // layouts already built come from the cache (the finalists, the final
-    // one).  The host layouts were ≈ half of the tuning's time (4096²: 1-2.4
-    // ms each against 1.7-2 ms of timing, PE_CTOR_TRACE=3,
-    // profiles/r6_ctor_tuning.txt).
-    struct Trial {
-      int ti;
-      std::string lay;
-    };
-    lay_cache_.clear();
-    lay_cache_on_ = true;
-    auto run_trials = [&](const std::vector<Trial>& trials) {
-      std::vector<float> out;
-      for (size_t i = 0; i <= trials.size(); ++i) {
-        const auto tl = clk::now();
-        if (i < trials.size()) {
-          lay_name_ = trials[i].lay;
-          set_items(trials[i].ti);
-          setup_items();  // (its upload waits for trial i-1's sweeps)
-        }
-        const auto tg = clk::now();
-        if (i > 0) {
-          PE_HIP_CHECK(hipEventSynchronize(t1_));
-          float ms = 0.f;
-          PE_HIP_CHECK(hipEventElapsedTime(&ms, t0_, t1_));
-          out.push_back(ms);
-          if (ctor_trace)
-            std::fprintf(stderr, "[pe] ctor   tune %3d rows %-5s %8.4f ms per sweep\n", trials[i - 1].ti,
-                         trials[i - 1].lay.c_str(), ms / float(kTimed));
-        }
-        if (i == trials.size()) break;
-        enqueue_init();
-        dev::launch_S(*kp_, 1, stream_);
-        dev::launch_S(*kp_, 0, stream_);
-        PE_HIP_CHECK(hipEventRecord(t0_, stream_));
-        for (int j = 0; j < kTimed; ++j) dev::launch_S(*kp_, (j + 1) & 1, stream_);
-        PE_HIP_CHECK(hipEventRecord(t1_, stream_));
-        if (ctor_trace)
-          std::fprintf(stderr, "[pe] ctor   tune %3d rows %-5s layout %7.3f ms\n", trials[i].ti, trials[i].lay.c_str(),
-                       1e3 * secs(tl, tg));
-      }
-      return out;
-    };
-    {
-      std::vector<Trial> tr;
-      for (int cand : cands) tr.push_back(Trial{cand, lay_name_});
-      const std::vector<float> ms = run_trials(tr);
-      for (size_t i = 0; i < tr.size(); ++i) {
-        ti_ms_.push_back(ms[i] / float(kTimed));
-        ti_rows_.push_back(tr[i].ti);
-        if (best_ms == 0.f || ms[i] < best_ms) {
-          best_ms = ms[i];
-          best = tr[i].ti;
-        }
-      }
-    }
-    // three-step: the other static layouts at the best height
-    std::string keep = lay_name_;
-    struct Tried {
-      int ti;
-      std::string lay;
-      float ms;
-    };
-    std::vector<Tried> tried;
-    for (size_t i = 0; i < ti_rows_.size(); ++i) tried.push_back(Tried{ti_rows_[i], lay_name_, ti_ms_[i] * float(kTimed)});
-    if (steps_ >= 3 && !std::getenv("PE_LAYOUT")) {
-      const std::string base = lay_name_;
-      std::vector<Trial> tr;
-      for (const char* alt : {"equal", "fill", "lpt"})
-        if (base != alt) tr.push_back(Trial{best, alt});
-      const std::vector<float> ms = run_trials(tr);
-      for (size_t i = 0; i < tr.size(); ++i) {
-        ti_ms_.push_back(ms[i] / float(kTimed));
-        ti_rows_.push_back(-best);  // (negative: a layout candidate at that height)
-        tried.push_back(Tried{best, tr[i].lay, ms[i]});
-        if (ms[i] < best_ms) {
-          best_ms = ms[i];
-          keep = tr[i].lay;
-        }
-      }
-    }
-    // Finalists: the two fastest candidates timed once more, each keeping its
-    // faster timing — the GPU clock ramps up during construction, so the first
-    // candidates were timed slow, and two within ≈2 % swapped places from one
-    // process to the next (2400×3200: equal layout at 80 rows or filling at
-    // 96, T_iterate 0.099 vs 0.095 s, profiles/r5_prio.txt).  Three-step only.
-    if (steps_ >= 3 && tried.size() >= 2) {
-      std::stable_sort(tried.begin(), tried.end(), [](const Tried& a, const Tried& b) { return a.ms < b.ms; });
-      const std::vector<float> ms = run_trials({Trial{tried[0].ti, tried[0].lay}, Trial{tried[1].ti, tried[1].lay}});
-      for (int f = 0; f < 2; ++f) {
-        Tried& t = tried[size_t(f)];
-        ti_ms_.push_back(ms[size_t(f)] / float(kTimed));
-        ti_rows_.push_back(t.lay == keep && t.ti == best ? best : -t.ti);
-        t.ms = std::min(t.ms, ms[size_t(f)]);
-      }
-      const Tried& w = tried[0].ms <= tried[1].ms ? tried[0] : tried[1];
-      best = w.ti;
-      keep = w.lay;
-    }
-    // the three best heights (any layout), for the overlap's own layout: its
-    // boundary-first filling list ranks them differently (8-rank slab of
-    // 8192²: 64, 80 and 96 rows tie within 1 % on the plain layout, 117-119 µs
-    // per sweep, but the overlapped sweep runs 146, 157 and 128 µs —
-    // profiles/r6_overlap_ti.txt)
-    std::stable_sort(tried.begin(), tried.end(), [](const Tried& a, const Tried& b) { return a.ms < b.ms; });
-    ti_alt_ = {best};
-    for (const Tried& t : tried)
-      if (ti_alt_.size() < 3 && std::find(ti_alt_.begin(), ti_alt_.end(), t.ti) == ti_alt_.end()) ti_alt_.push_back(t.ti);
-    lay_name_ = keep;
-    set_items(best);
-    setup_items();
-    lay_cache_on_ = false;
-    lay_cache_.clear();
-  }
+  if (tune_ti_ && !resident_) tune_rows_per_item(ti_cands, ti);
   if (fused_ && std::getenv("PE_STAMPS") && std::atoi(std::getenv("PE_STAMPS")) == 1) {
     const size_t nw = size_t(dev::kWPB) * size_t(std::max(k.nblocks, k.nblocks0));
     nstamps_ = 4 * size_t(nslot_cap_) + 2 * nw + 32 * nw + 8;  // (+8 whole-grid stamps: three-step sweep)
@@ -683,7 +478,7 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
   // it: the push is delivered by the in-sweep sum's flags, so the local
   // sweeps above ran without either).
   if (push_ok_) {
-    const int64_t side = int64_t(hdep_) * k.pitch;
+    const int64_t side = int64_t(geo_.hdep) * k.pitch;
     double* lo = static_cast<double*>(hpeers_[size_t(blk_.nbr[LEFT] >= 0 ? blk_.nbr[LEFT] : blk_.rank)]);
     double* hi = static_cast<double*>(hpeers_[size_t(blk_.nbr[RIGHT] >= 0 ? blk_.nbr[RIGHT] : blk_.rank)]);
     for (int b = 0; b < 2; ++b) {
@@ -745,8 +540,7 @@ void DeviceSolver::relayout(int ti, int order) {
   PE_HIP_CHECK(hipStreamSynchronize(stream_));
   for (auto& g : graphs_) PE_HIP_CHECK(hipGraphExecDestroy(g.second));
   graphs_.clear();
-  set_items(ti);
-  setup_items();
+  apply_layout(ti);
 }
 
 void DeviceSolver::set_check_tol(bool on) {
@@ -768,13 +562,13 @@ void DeviceSolver::set_fused_fields(double* x0, double* x1, double* w) {
   xalt_ = x1;
   walt_ = w;
   // local (0, 0): row -(hdep-1), column -xorg at element 0
-  const int64_t h = hdep_ - 1, hc = xorg_;
+  const int64_t h = geo_.hdep - 1, hc = geo_.xorg;
   k.x[0] = x0 + h * k.pitch + hc;
   k.x[1] = x1 + h * k.pitch + hc;
-  k.w = w + h * plane_ + hc;
+  k.w = w + h * geo_.plane + hc;
   k.r = k.x[0];
-  k.p[0] = k.x[0] + plane_;
-  k.p[1] = k.x[1] + plane_;
+  k.p[0] = k.x[0] + geo_.plane;
+  k.p[1] = k.x[1] + geo_.plane;
 }
 
 // Median time of this rank's halo exchange (every rank runs the same
@@ -881,13 +675,13 @@ void DeviceSolver::upload(void* dst, const void* src, size_t bytes) {
 }
 
 void DeviceSolver::build_tables(int64_t rows_hi, int64_t cols_hi) {
-  const std::vector<double> t = chord_tables(prob_, blk_, rows_hi, cols_hi, tab_lo_);
+  const std::vector<double> t = chord_tables(prob_, blk_, rows_hi, cols_hi, geo_.tab_lo);
   const auto t0 = clk::now();
   upload(tables_, t.data(), sizeof(double) * t.size());
   copy_setup_s_ += secs(t0, clk::now());
   const double* col = t.data();
-  const double* row = t.data() + (rows_hi - tab_lo_ + 1) * 4;
-  rowcls_host_ = row_classes(col, row, rows_hi, cols_hi, tab_lo_);
+  const double* row = t.data() + (rows_hi - geo_.tab_lo + 1) * 4;
+  rowcls_host_ = row_classes(col, row, rows_hi, cols_hi, geo_.tab_lo);
   const std::vector<int>& rc = rowcls_host_;
   const auto t1 = clk::now();
   upload(rowcls_, rc.data(), sizeof(int) * rc.size());
@@ -914,7 +708,7 @@ std::vector<DeviceSolver::HaloPhase> DeviceSolver::halo_phases(int buf) const {
   // Phase 0: y strips (2·hdep values per owned row: r and p of hdep columns;
   // the single sweep stores them from inside the sweep, the multi-step
   // sweeps' are packed after it — enqueue_exchange).
-  const int64_t c = 2 * int64_t(hdep_) * blk_.nx;
+  const int64_t c = 2 * int64_t(geo_.hdep) * blk_.nx;
   if (blk_.has(DOWN)) ph[0].ex.push_back(Exchange{DOWN, blk_.nbr[DOWN], k.send_dn, const_cast<double*>(k.recv_dn), c});
   if (blk_.has(UP)) ph[0].ex.push_back(Exchange{UP, blk_.nbr[UP], k.send_up, const_cast<double*>(k.recv_up), c});
   ph[0].unpack = blk_.has(DOWN) || blk_.has(UP);
@@ -923,7 +717,7 @@ std::vector<DeviceSolver::HaloPhase> DeviceSolver::halo_phases(int buf) const {
   // neighbour): rows 1..h → the LEFT neighbour's rows nx'+1..nx'+h, rows
   // nx-h+1..nx → the RIGHT neighbour's rows 1-h..0.
   double* x = k.x[buf];
-  const int64_t h = hdep_, n = h * k.pitch, hc = xorg_;  // (whole rows: from column -xorg)
+  const int64_t h = geo_.hdep, n = h * k.pitch, hc = geo_.xorg;  // (whole rows: from column -xorg)
   if (blk_.has(LEFT))
     ph[1].ex.push_back(Exchange{LEFT, blk_.nbr[LEFT], x + 1 * k.pitch - hc, x + (1 - h) * k.pitch - hc, n});
   if (blk_.has(RIGHT))
@@ -959,11 +753,11 @@ double* DeviceSolver::fs2_dev(int par) { return st_->fs2[par]; }
 double* DeviceSolver::err_dev() { return st_->err; }
 
 void DeviceSolver::enqueue_init() {
-  const int64_t n = fused_ ? 2 * xsize_ + wsize_ : 4 * blk_.alloc;
+  const int64_t n = fused_ ? 2 * geo_.xsize + geo_.wsize : 4 * blk_.alloc;
   if (fused_) {
-    PE_HIP_CHECK(hipMemsetAsync(fields_, 0, sizeof(double) * xsize_, stream_));
-    PE_HIP_CHECK(hipMemsetAsync(xalt_, 0, sizeof(double) * xsize_, stream_));
-    PE_HIP_CHECK(hipMemsetAsync(walt_, 0, sizeof(double) * wsize_, stream_));
+    PE_HIP_CHECK(hipMemsetAsync(fields_, 0, sizeof(double) * geo_.xsize, stream_));
+    PE_HIP_CHECK(hipMemsetAsync(xalt_, 0, sizeof(double) * geo_.xsize, stream_));
+    PE_HIP_CHECK(hipMemsetAsync(walt_, 0, sizeof(double) * geo_.wsize, stream_));
   } else {
     PE_HIP_CHECK(hipMemsetAsync(fields_, 0, sizeof(double) * n, stream_));
   }
@@ -1032,14 +826,12 @@ void DeviceSolver::enqueue_iteration(int par, int mlimit) {
   if (fused_ && overlap_) {
     KParams ko = *kp_;
     ko.ilist = ilist_;
-    ko.lnsh = ov_lnsh_;
-    for (int x = 0; x <= 8; ++x) ko.lbase[x] = ov_lbase_[x];
-    for (int x = 0; x < 8; ++x) ko.lnb[x] = ov_lnb_[x];
-    ko.nblocks = std::max(ov_lnsh_, kp_->nblocks - ov_reserve_);
-    ko.nblocks0 = std::max(ov_lnsh_, kp_->nblocks0 - ov_reserve_);
+    for (int x = 0; x < 8; ++x) ko.lnb[x] = lay_.lnb[x];  // (lnsh, lbase: the plain launch's)
+    ko.nblocks = std::max(lay_.lnsh, kp_->nblocks - lay_req_.ov_reserve);
+    ko.nblocks0 = std::max(lay_.lnsh, kp_->nblocks0 - lay_req_.ov_reserve);
     ko.mlimit = mlimit;
     ov_epoch_ += 1;
-    const unsigned long long target = ov_epoch_ * (unsigned long long)(ov_nb_);
+    const unsigned long long target = ov_epoch_ * (unsigned long long)(lay_.nbnd);
     mark_begin(kPhSweep, stream_);
     dev::launch_S(ko, par, stream_, false);  // boundary items first in every shard
     mark_end(stream_);
@@ -1048,7 +840,7 @@ void DeviceSolver::enqueue_iteration(int par, int mlimit) {
       dev::launch_red(ko, par, stream_);
       mark_end(stream_);
     }
-    if (ov_debug_ & 2) {
+    if (lay_req_.knobs.ov_debug & 2) {
       dev::launch_wait_sig(ko, target, stream_);
       mark_begin(kPhHalo, stream_);
       enqueue_exchange(par);
@@ -1603,7 +1395,7 @@ void DeviceSolver::copy_w(double* host, bool owned_only) {
 }
 
 int64_t DeviceSolver::field_rows() const { return fused_ ? blk_.nx + 4 : blk_.rows; }
-int64_t DeviceSolver::field_cols() const { return fused_ ? plane_ : blk_.pitch; }
+int64_t DeviceSolver::field_cols() const { return fused_ ? geo_.plane : blk_.pitch; }
 
 void DeviceSolver::copy_field(int which, double* host) {
   const KParams& k = *kp_;
@@ -1613,8 +1405,8 @@ void DeviceSolver::copy_field(int which, double* host) {
     const double* base = which == 0 ? k.x[0] : which == 1 ? k.w : which == 2 ? k.x[0] + k.poff
                          : which == 3 ? k.x[1] + k.poff : k.x[1];
     const int64_t stride = which == 1 ? k.wpitch : k.pitch;
-    PE_HIP_CHECK(hipMemcpy2DAsync(host, sizeof(double) * plane_, base - stride - 1, sizeof(double) * stride,
-                                  sizeof(double) * plane_, blk_.nx + 4, hipMemcpyDeviceToHost, stream_));
+    PE_HIP_CHECK(hipMemcpy2DAsync(host, sizeof(double) * geo_.plane, base - stride - 1, sizeof(double) * stride,
+                                  sizeof(double) * geo_.plane, blk_.nx + 4, hipMemcpyDeviceToHost, stream_));
   } else {
     const double* src = which == 0 ? k.r : which == 1 ? k.w : which == 2 ? k.p[0] : k.p[1];
     PE_HIP_CHECK(hipMemcpyAsync(host, src, sizeof(double) * blk_.rows * k.pitch, hipMemcpyDeviceToHost, stream_));

@@ -53,8 +53,8 @@ void DeviceSolver::setup_halo_push() {
   // the real stores and loads), so a row slab's per-rank time includes what
   // the 8-GPU job's push kernel does
   if (const char* e = std::getenv("PE_PUSH_LOOPBACK"); allowed && e && std::atoi(e) == 1 && comm_->size() > 1 &&
-                                                       fused_ && blk_.Py == 1 && (prob_.M - 1) / blk_.Px >= 2 * hdep_) {
-    const size_t bytes = sizeof(double) * 4 * size_t(hdep_) * size_t(kp_->pitch);
+                                                       fused_ && blk_.Py == 1 && (prob_.M - 1) / blk_.Px >= 2 * geo_.hdep) {
+    const size_t bytes = sizeof(double) * 4 * size_t(geo_.hdep) * size_t(kp_->pitch);
     void* buf = nullptr;
     PE_HIP_CHECK(hipExtMallocWithFlags(&buf, bytes, hipDeviceMallocFinegrained));
     PE_HIP_CHECK(hipMemsetAsync(buf, 0, bytes, stream_));
@@ -70,13 +70,13 @@ void DeviceSolver::setup_halo_push() {
                  : "";
   if (!push_status_.empty()) return;
   push_status_ = "off: slabs thinner than 2 halo depths";
-  if ((prob_.M - 1) / blk_.Px < 2 * hdep_) return;  // edge rows 1..h and nx-h+1..nx distinct
+  if ((prob_.M - 1) / blk_.Px < 2 * geo_.hdep) return;  // edge rows 1..h and nx-h+1..nx distinct
   push_status_ = "off: PE_XR=0";
   if (const char* e = std::getenv("PE_XR"); e && std::atoi(e) == 0) return;
   push_status_ = std::string("off: PE_HALO=") + (hm ? hm : "");
   if (!allowed) return;
   push_status_ = "fallback: the receive buffers could not be mapped on every rank";
-  const size_t bytes = sizeof(double) * 4 * size_t(hdep_) * size_t(kp_->pitch);  // [parity][side][hdep rows]
+  const size_t bytes = sizeof(double) * 4 * size_t(geo_.hdep) * size_t(kp_->pitch);  // [parity][side][hdep rows]
   void* buf = nullptr;
   if (hipExtMallocWithFlags(&buf, bytes, hipDeviceMallocFinegrained) != hipSuccess) {
     buf = nullptr;
@@ -103,7 +103,7 @@ void DeviceSolver::setup_halo_push() {
   // sweep can push.
   {
     KParams t = *kp_;
-    const int64_t side = int64_t(hdep_) * t.pitch;
+    const int64_t side = int64_t(geo_.hdep) * t.pitch;
     for (int b = 0; b < 2; ++b) {
       t.hpush_lo[b] = blk_.has(LEFT) ? static_cast<double*>(hpeers_[size_t(blk_.nbr[LEFT])]) + (2 * b + 1) * side
                                      : nullptr;
@@ -176,7 +176,7 @@ void DeviceSolver::setup_halo_put() {
     for (const Exchange& e : p.ex) cmax = std::max(cmax, e.count);
   // (every rank takes part in the collectives below, a rank without
   // neighbours too: its buffer simply stays unused)
-  cmax = std::max<int64_t>({cmax, 2 * int64_t(hdep_) * blk_.nx, int64_t(hdep_) * kp_->pitch});
+  cmax = std::max<int64_t>({cmax, 2 * int64_t(geo_.hdep) * blk_.nx, int64_t(geo_.hdep) * kp_->pitch});
   put_stride_ = (cmax + dev::kPutBoxOff + 31) / 32 * 32;  // (+ the slot's 16-B phase offset)
   const size_t flag_bytes = sizeof(unsigned long long) * 4 * dev::kPutParts * dev::kPutFlagStride;
   const size_t bytes = flag_bytes + sizeof(double) * 4 * 2 * size_t(put_stride_);
@@ -322,17 +322,15 @@ void DeviceSolver::apply_halo_path(const std::string& path, bool overlap, bool l
   want_overlap_ = overlap;
   for (auto& g : graphs_) PE_HIP_CHECK(hipGraphExecDestroy(g.second));  // captured on the old path
   graphs_.clear();
-  if (ti > 0 && ti != kp_->ti) {  // (another height for the overlap's layout)
-    set_items(ti);
-    relay = true;
-  }
+  const int nti = ti > 0 ? ti : kp_->ti;  // (another height for the overlap's layout)
+  relay = relay || nti != kp_->ti;
   // the overlap's boundary-first list, or the plain one (the exchange, the put
   // and the push share the plain layout: no re-layout between them)
   const bool relaid = relay || overlap_ != (overlap && !push_);
   if (relaid) {
     const auto t0 = clk::now();
     const double up0 = copy_setup_s_;
-    setup_items();
+    apply_layout(nti);
     if (live && std::getenv("PE_CTOR_TRACE") && std::atoi(std::getenv("PE_CTOR_TRACE")) >= 2)
       std::fprintf(stderr, "[pe] halo path re-layout %s at %d rows: %6.3f ms (list upload %6.3f ms)\n",
                    overlap_ ? "overlap" : "plain", kp_->ti, 1e3 * secs(t0, clk::now()), 1e3 * (copy_setup_s_ - up0));
@@ -380,7 +378,7 @@ void DeviceSolver::choose_halo_path() {
   const char* ov = std::getenv("PE_OVERLAP");
   // (the two-step sweep has no boundary-item signal; every rank decides this
   // from global inputs — a rank without neighbours still takes part, its
-  // overlap is simply off in setup_items)
+  // overlap is simply off in apply_layout)
   const bool ov_able = !sstep_ || steps_ >= 3;
   struct Cand {
     std::string path;
@@ -443,7 +441,7 @@ void DeviceSolver::choose_halo_path() {
   Range range("pe.choose_halo_path");
   lay_cache_.clear();
   lay_cache_on_ = true;
-  if (fused_) lay_cache_[{kp_->ti, overlap_, lay_name_}] = snap_layout();  // (the construction's)
+  if (!lay_.list.empty()) lay_cache_[{kp_->ti, overlap_, lay_name_}] = lay_;  // (the construction's)
   const int keep_tol = kp_->check_tol;
   kp_->check_tol = 0;
   // (PE_CTOR_TRACE=1: rank 0's candidate times; 2: every rank's, with the

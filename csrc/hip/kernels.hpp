@@ -22,6 +22,8 @@
 
 #include <cstdint>
 
+#include "pe/item_layout.hpp"  // item-entry and strip constants (kBandBit, kWPB, kFSW, …)
+
 namespace pe {
 namespace dev {
 
@@ -184,7 +186,7 @@ struct KParams {
   long long fault_zero;          // > 0: zero the (p, A p) sums after this iteration → breakdown (zero@iter:K)
   double* hist;                  // keep_history: ‖Δw‖ of iteration k at hist[k-1] (k ≤ hist_n)
   long long hist_n;
-  // Item lists (dynamic sweeps, setup_items): entries {first row, strip |
+  // Item lists (pe/item_layout.hpp, DeviceSolver::apply_layout): entries {first row, strip |
   // rows << 20}, split into lnsh shards; shard x owns ilist[lbase[x] ..
   // lbase[x+1]) and (halo/interior overlap) its first lnb[x] entries are
   // boundary items (outputs sent to a neighbour), each of which bumps st->sig
@@ -248,29 +250,8 @@ struct KParams {
 constexpr int kReplay3 = -2;
 
 constexpr int kTJ = 256;         // threads per block (4 wave64s)
-constexpr int kWPB = 4;          // waves per block
-constexpr int kSW = 128;         // columns per wave strip (2 per lane, 16-B accesses)
-constexpr int kTImax = 62;       // max rows per work item (rows ib-1..ie+1 live one per lane)
-// Item-list entries {first row | band flag, strip | rows << 20}: kBandBit set
-// when the item's rows ib-2 .. ie+2 contain a boundary-band row in its strip
-// (general march); clear → the plain unrolled march.
-constexpr int kBandBit = 1 << 30;
-constexpr int kRowMask = kBandBit - 1;
-// Three-step sweep only: kUniBit set when every row ib-6 .. ie+6 of the item
-// lies wholly inside or wholly outside the interior in its strip's window
-// (the kernel's uniform-row march: three scalars per row, no lane tests).
-constexpr int kUniBit = 1 << 29;
-constexpr int kRowMask3 = kUniBit - 1;
-constexpr int kFSW = 124;        // fused sweep: output columns per wave strip (128 loaded, 2-column halo per side)
-constexpr int kFSW2 = 120;       // two-step sweep: output columns per strip (4-column halo per side)
 constexpr int kNS2 = 20;         // two-step sweep: sums per sweep
-constexpr int kTImax2 = 48;      // two-step sweep: max rows per item (rows ib-4 .. ie+5 live one per lane)
-constexpr int kFSW3 = 48;        // three-step sweep: output columns per 64-column strip (one per lane; 6-column halo needed per side)
-constexpr int kHL3 = 8;          // three-step sweep: left halo lanes of a strip (right: 64 - kFSW3 - kHL3); with the
-                                 // rows' element 0 at column -(kHL3 - 1), every strip's loads are whole 128-B lines
-                                 // and its outputs whole 64-B segments
 constexpr int kNS3 = 19;         // three-step sweep: sums per sweep
-constexpr int kTImax3 = 512;     // three-step sweep: max rows per item (row windows reload every ~58 rows)
 
 // LDS-resident single sweep (resident.hip): small single-rank blocks run many
 // iterations in ONE launch.  The block is cut into tiles of one 124-column

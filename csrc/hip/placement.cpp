@@ -149,7 +149,7 @@ bool DeviceSolver::placement_search(bool retry) {
     const double frac = 0.4;
     size_t free_b = 0, total_b = 0;
     if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-      const double per_try = skip_gb * double(1ull << 30) + double(sizeof(double) * (2 * xsize_ + wsize_));
+      const double per_try = skip_gb * double(1ull << 30) + double(sizeof(double) * (2 * geo_.xsize + geo_.wsize));
       tries = std::min<int>(tries, std::max(1, int(frac * double(free_b) / per_try)));
     }
   }
@@ -165,7 +165,7 @@ bool DeviceSolver::placement_search(bool retry) {
   // and candidates were freed: the allocator would hand them out again)
   const size_t n_first = placement_ms_.size();
   if (retry && skip_gb > 0) {
-    const double gb = double(n_first) * (skip_gb + double(sizeof(double) * (2 * xsize_ + wsize_)) / double(1ull << 30));
+    const double gb = double(n_first) * (skip_gb + double(sizeof(double) * (2 * geo_.xsize + geo_.wsize)) / double(1ull << 30));
     void* sp = nullptr;
     if (hipMalloc(&sp, size_t(gb * double(1ull << 30))) == hipSuccess) spacers.push_back(sp);
     else (void)hipGetLastError();
@@ -176,14 +176,14 @@ bool DeviceSolver::placement_search(bool retry) {
       void* sp = nullptr;
       if (skip_gb > 0 && hipMalloc(&sp, size_t(skip_gb * double(1ull << 30))) != hipSuccess) break;
       if (sp) spacers.push_back(sp);
-      void* a = field_try_alloc(sizeof(double) * xsize_);
+      void* a = field_try_alloc(sizeof(double) * geo_.xsize);
       if (!a) break;
-      void* b = field_try_alloc(sizeof(double) * xsize_);
+      void* b = field_try_alloc(sizeof(double) * geo_.xsize);
       if (!b) {
         field_free(a);
         break;
       }
-      void* w = field_try_alloc(sizeof(double) * wsize_);
+      void* w = field_try_alloc(sizeof(double) * geo_.wsize);
       if (!w) {
         field_free(a);
         field_free(b);

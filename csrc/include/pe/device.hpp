@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "pe/comm.hpp"
+#include "pe/row_classes.hpp"  // host tables, row classes, the item-layout planner
 #include "pe/solver.hpp"
 
 #define PE_HIP_CHECK(expr)                                                                     \
@@ -224,15 +225,16 @@ class DeviceSolver {
   const std::vector<int>& ti_tuning_rows() const { return ti_rows_; }  // the candidates
   // static layout: {most loaded wave, mean wave load, max items on a wave}
   // in row-step cost units (0s for a dynamic layout)
-  std::vector<double> layout_load() const { return {lay_max_, lay_mean_, double(lay_items_)}; }
-  int layout_cuts() const { return lay_cuts_; }
+  std::vector<double> layout_load() const { return {lay_.max, lay_.mean, double(lay_.items)}; }
+  int layout_cuts() const { return lay_.cuts; }
   // the static layout in use: "lpt", "fill" or "equal" (three-step sweep)
-  const std::string& layout_name() const { return lay_used_; }
+  const std::string& layout_name() const { return lay_.name; }
   // the item list as laid out (host copy of KParams::ilist; empty for walks
   // without a list): {first row | flags, strip | rows << 20} per position
-  const std::vector<int2>& layout_entries() const { return ilist_host_; }
+  const std::vector<Entry>& layout_entries() const { return lay_.list; }
   // overlap: list positions 0 .. n-1 hold the boundary items (0: no overlap)
-  int layout_boundary() const { return overlap_ ? ov_lnb_[0] : 0; }
+  int layout_boundary() const { return overlap_ ? lay_.lnb[0] : 0; }
+  const LayoutRequest& layout_request() const { return lay_req_; }  // what that list was asked with (occupancy, knobs)
   // First cross-device run diagnostics: hipDeviceCanAccessPeer of this
   // rank's device toward each rank's (1 / 0; -1 the same device; empty on
   // one rank), why the halo push is on / off / fell back, and the transport
@@ -268,13 +270,16 @@ class DeviceSolver {
   void build_tables(int64_t rows_hi, int64_t cols_hi);
   void upload(void* dst, const void* src, size_t bytes);  // set-up data via pinned staging + copy kernel
   void set_fused_fields(double* x0, double* x1, double* w);
-  void setup_items();  // item lists: static LPT layout or dynamic per-XCD shards (+ halo/interior overlap)
+  // item lists at `ti` rows per item: static layout or dynamic per-XCD shards (+ halo/interior overlap)
+  void apply_layout(int ti);
+  // the planner's (or the cache's) layout on that halo path; the PE_* layout knobs are read here
+  ItemLayout plan_layout(int ti, bool want_overlap, bool push, LayoutRequest* asked);
+  void tune_rows_per_item(const std::vector<int>& cands, int ti);  // times the candidates, keeps the fastest
   void create_halo_stream();
   void choose_placement();   // local search, then (multi-rank) the coordinated retry round
   bool placement_search(bool retry);  // local; true when the kept candidate is in the best class
   void measure_exchange();  // sets exchange_us_ (collective)
   void setup_resident();    // tile geometry, band-table size, buffers (single rank, small blocks)
-  void set_items(int ti);   // item counts and persistent grids for `ti` rows per item
   void enqueue_iteration(int par, int mlimit = 0);  // mlimit > 0: a partial three-step sweep
   void enqueue_fs_reduce(int par);  // cross-rank sum of sweep sums (no-op when the sweep does it)
   // after_sweep: the halo of `buf` was produced by a sweep (with the halo
@@ -285,21 +290,9 @@ class DeviceSolver {
   // collective: time the available halo paths (exchange / put / push, with and
   // without the overlap) for a few sweeps each and keep the fastest (max over ranks)
   void choose_halo_path();
-  // Item lists already laid out, while the rows per item are tuned and the
-  // halo path is chosen (their candidates come back to layouts already built:
-  // 0.3-2.6 ms of host work each)
-  struct LayoutSnap {
-    std::vector<int2> list;
-    int static_waves, ov_nb, ov_lnsh, ov_lbase[9], ov_lnb[8], lay_items, lay_cuts;
-    double lay_max, lay_mean;
-    std::string lay_used;
-    int lnsh, lwaves, nslots, lbase[9], lnb[8], nblocks, nblocks0;
-  };
   // switch path + re-lay the items; live: the iteration state carries on (halo moved between x and the push buffer)
   // ti > 0: rows per item of the overlap's layout (another height than the tuning's)
   void apply_halo_path(const std::string& path, bool overlap, bool live = false, int ti = 0);
-  LayoutSnap snap_layout() const;
-  void restore_layout(const LayoutSnap& v);
   void prepare_layout(int ti, bool overlap);  // into the cache, host only (item_layout.cpp)
   // one halo phase through the put kernel (put_) or the comm
   void xfer(const std::vector<Exchange>& ex, hipStream_t s);
@@ -340,15 +333,11 @@ class DeviceSolver {
   bool fused_ = false;
   bool sstep_ = false;    // multi-iteration sweep (fused2.hip / fused3.hip): steps_ iterations per launch
   int steps_ = 1;         // iterations per sweep launch (1, 2, 3)
-  int fsw_ = 124;         // output columns per strip (kFSW / kFSW2 / kFSW3)
-  int hdep_ = 2;          // halo depth of the single-sweep layouts (2 / 4 / 6)
-  int xorg_ = 1;          // columns stored left of column 0 (KParams::xorg)
-  int64_t tab_lo_ = -1;   // first local index of the chord tables / row classes
+  SweepGeometry geo_;     // strips, planes, halo depth, table ranges (pe/item_layout.hpp)
   double* fields_ = nullptr;  // classic: r, w, p0, p1 (alloc each); single-sweep: x0, x1, w
   double* xalt_ = nullptr;    // single-sweep: x1 (separate allocation)
   double* walt_ = nullptr;    // single-sweep: w
   std::vector<float> placement_ms_;  // per-candidate sweep time of the placement search
-  int64_t xsize_ = 0, wsize_ = 0, plane_ = 0;
   double* tables_ = nullptr;
   int* rowcls_ = nullptr;
   std::vector<int> rowcls_host_;  // host copy of the row classes (item cost estimates)
@@ -362,13 +351,7 @@ class DeviceSolver {
   bool overlap_ = false;
   int2* ilist_ = nullptr;  // per shard: boundary items, heavy items, the rest (dev::KParams::ilist)
   size_t ilist_cap_ = 0;   // entries allocated at ilist_
-  std::vector<int> pgen_, pmix_;  // item layout: per strip, prefix counts of band / mixed rows (item_layout.cpp)
-  std::vector<std::array<int64_t, 4>> eq_runs_[2];  // equal-cost layout: runs {first row, rows, strip, kind} (no overlap / overlap)
   int nslot_cap_ = 0;      // item-sum slots allocated
-  int ov_lnsh_ = 1, ov_nb_ = 0, ov_reserve_ = 8, ov_debug_ = 0;
-  int wave_cap_ = 0;     // resident waves of the sweep grid (occupancy)
-  int static_waves_ = 0; // static list walk: waves the list is laid out for (0: no static list)
-  int ov_lbase_[9] = {}, ov_lnb_[8] = {};
   unsigned long long ov_epoch_ = 0;  // overlapped sweeps since the state was last cleared (sig targets)
   hipStream_t hs_ = nullptr;
   hipEvent_t ev_halo_ = nullptr;
@@ -402,17 +385,13 @@ class DeviceSolver {
   std::vector<float> ti_ms_;      // their per-sweep times
   std::vector<int> ti_rows_;      // the candidates timed
   std::vector<int> ti_alt_;       // the tuning's best two heights (the overlap is timed at both)
-  double lay_max_ = 0, lay_mean_ = 0;  // static layout: heaviest / mean wave load (row steps)
-  int lay_items_ = 0;                  // static layout: most items on one wave
-  int lay_cuts_ = 0;                   // three-step filling layout: items cut to fill the waves
-  // three-step static layout: lay_name_ the construction's choice (by block
-  // size / rows-per-item tuning; PE_LAYOUT overrides), lay_used_ the last laid out
-  std::string lay_name_ = "lpt", lay_used_ = "lpt";
+  std::string lay_name_ = "lpt";  // three-step static layout: the construction's choice (PE_LAYOUT overrides)
+  std::unique_ptr<LayoutPlanner> planner_;  // host-only (pe/item_layout.hpp); built after the row classes
+  ItemLayout lay_;                          // the list the sweeps walk (uploaded at ilist_)
+  LayoutRequest lay_req_;                   // what lay_ was asked with
   std::vector<int> peer_access_;
-  std::vector<int2> ilist_host_;
-  std::map<std::tuple<int, bool, std::string>, LayoutSnap> lay_cache_;  // (rows per item, overlap, layout name)
+  std::map<std::tuple<int, bool, std::string>, ItemLayout> lay_cache_;  // (rows per item, overlap, layout name)
   bool lay_cache_on_ = false;
-  bool lay_dry_ = false;                   // setup_items lays out for the cache only (no upload)
   std::function<void()> halo_idle_;        // host work while time_halo_path's sweeps run (the choice's next layouts)
   std::string push_status_ = "off", xr_status_ = "none";
   int wave_caps_[2] = {0, 0};     // resident waves of the applying / deferring sweep
@@ -432,7 +411,7 @@ class DeviceSolver {
   bool put_ = false;                // halo phases through kPut (peer put) instead of comm_->exchange
   bool put_ok_ = false;             // put set up and self-tested on every rank: a halo-path candidate
   bool put_loop_ = false;           // PE_PUT_LOOPBACK: this rank is its own peer (one-GPU probes / tests)
-  bool want_overlap_ = false;       // the chosen path's overlap (setup_items)
+  bool want_overlap_ = false;       // the chosen path's overlap (apply_layout)
   bool shared_dev_ = false;         // another rank of the job runs on this rank's GPU (test jobs)
   void* put_buf_ = nullptr;         // fine-grained: [4 dirs][kPutParts] flags, then [4 dirs][2][put_stride_] inbox
   std::vector<void*> put_peers_;    // every rank's put_buf_ mapped here
@@ -446,28 +425,6 @@ class DeviceSolver {
   std::vector<void*> hpeers_;       // every rank's receive buffer mapped here (comm_->map_peer_buffers)
   double exchange_us_ = 0;  // measured halo exchange (max over ranks), multi-rank only  // the first solve() carries the construction time
 };
-
-// Per-row coefficient classes from the chord tables (see row_classes.cpp):
-// for each local row q ∈ [-1, rows_hi-1], {in_lo, in_hi, out_lo, out_hi} such
-// that every face coefficient of node (q, lj) is exactly 1 for lj ∈ [in_lo,
-// in_hi] and exactly 1/eps for lj ∉ [out_lo, out_hi], lj ∈ [-1, cols_hi].
-// Conservative: anything else is evaluated exactly.  (rows_hi+2) × 4 ints.
-// Tables and classes start at local index `lo` (-1; the two-step sweep's
-// 4-deep halo: -4): entry of local q at (q - lo).
-std::vector<int> row_classes(const double* colT, const double* rowT, int64_t rows_hi, int64_t cols_hi,
-                             int64_t lo = -1);
-// Chord tables of a block: (rows_hi+2)×4 column entries {halfA, sB, eB, x}
-// for li ∈ [-1, rows_hi], then (cols_hi+2)×4 row entries {sA, eA, halfB, y}
-// for lj ∈ [-1, cols_hi]; indexed by local index + 1.  The classic kernels
-// use rows_hi = nx+2, cols_hi = ny+2; the single-sweep kernel reaches two
-// halo nodes further and past ny into strip padding.
-std::vector<double> chord_tables(const Problem& P, const Block& blk, int64_t rows_hi, int64_t cols_hi,
-                                 int64_t lo = -1);
-// Host mirror of the kernels' coefficient path for local (li, lj) ∈
-// [0, nx+1] × [0, ny+1]: a(li, lj), b(li, lj) and the class (0 interior,
-// 1 exterior, 2 boundary band).  Row-major (nx+2) × (ny+2).
-void host_coefficients(const Problem& P, const Block& blk, std::vector<double>& a, std::vector<double>& b,
-                       std::vector<int>& cls);
 
 // P virtual ranks on ONE device (LocalComm).  Every rank runs the
 // same kernels and the same halo plan as under RCCL; the transport is

@@ -1,12 +1,17 @@
-"""MI355X tests of the static item layouts (csrc/hip/item_layout.cpp): every
+"""MI355X tests of the item layouts of live solvers (planned on the host by
+csrc/core/item_layout.cpp, applied by csrc/hip/item_layout.cpp): every
 owned row of every strip is marched exactly once, whatever the layout — the
 three-step filling layout (kind-aware costs, items cut to fill each wave),
 the equal-cost layout (PE_LAYOUT=equal), the LPT layout (PE_LAYOUT=lpt) and
 the overlap's boundary-first order — and the equal-cost layout evens the
-waves' estimated loads.  Construction only (no solve)."""
+waves' estimated loads; the list a live solver walks is the one the host
+planner builds from the solver's own request (test_item_layout.py tests the
+planner without a device).  Construction only (no solve)."""
 
 import numpy as np
 import pytest
+
+import layout_checks
 
 from poisson_ellipse_openmp_mpi_cuda_amd import EllipseProblem
 from poisson_ellipse_openmp_mpi_cuda_amd.parallel import decomp as D
@@ -16,38 +21,14 @@ BAND, UNI = 1 << 30, 1 << 29
 
 
 def _coverage(s, nx, ny):
-    ent = [e for e in s.layout_entries if e[1] > 0]
-    nstrips = s.strips
-    assert nstrips == (ny + 47) // 48  # 48 output columns per three-step strip (fused3.hip)
-    cov = np.zeros((nstrips, nx + 1), dtype=np.int32)
-    for ib, rows, strip, _flags in ent:
-        assert 0 <= strip < nstrips and ib >= 1 and ib + rows - 1 <= nx
-        cov[strip, ib:ib + rows] += 1
-    assert (cov[:, 1:] == 1).all(), "a row of a strip is marched twice or never"
-    return ent
+    return layout_checks.coverage(s.layout_entries, s.strips, nx, ny)
 
 
 def _boundary_first(s, blk):
-    """Overlap: the kernel's kSignal variant counts list positions 0 .. nb-1
-    as the boundary items (outputs a neighbour needs: the 6 owned rows /
-    columns next to it) and starts the exchange when they are stored — so
-    those positions hold exactly the boundary items."""
-    nb = s.layout_boundary
-    assert nb > 0
-    nx, ny = blk.nx, blk.ny
-    has = [blk.nbr[i] >= 0 for i in range(4)]  # LEFT, RIGHT, DOWN, UP
-
-    def bnd(ib, rows, strip):
-        j0 = -7 + 48 * strip
-        jlo, jhi = max(1, j0 + 8), min(ny, j0 + 55)
-        return ((has[0] and ib <= 6) or (has[1] and ib + rows - 1 >= nx - 5) or (has[2] and jlo <= 6)
-                or (has[3] and jhi >= ny - 5))
-
+    """Overlap: list positions 0 .. layout_boundary-1 hold exactly the boundary
+    items (layout_checks.boundary_first)."""
     ents = s.layout_entries
-    for pos, (ib, rows, strip, _flags) in enumerate(ents):
-        if rows == 0:
-            continue
-        assert bnd(ib, rows, strip) == (pos < nb), (pos, nb, ib, rows, strip)
+    layout_checks.boundary_first(ents, blk.nbr, blk.nx, blk.ny, [0, len(ents)], [s.layout_boundary])
 
 
 @pytest.mark.parametrize("P,spec,env", [(1, "device", {}), (1, "device", {"PE_LAYOUT": "equal"}),
@@ -75,9 +56,7 @@ def test_layout_covers_every_row_once(gpu, nat, monkeypatch, P, spec, env):
         # exactly k pieces per wave, estimated loads within a few percent (with
         # the overlap, the 6-row boundary pieces cut off for the exchange are
         # a wave's whole share on small blocks: no balance bound there)
-        assert mx <= 1.10 * mean, (mx, mean)  # (8192² at 112 rows: 7 pieces per wave, 1.09)
-        ent = [e for e in s.layout_entries if e[1] > 0]
-        assert (per - 1) * s.layout_waves < len(ent) <= per * s.layout_waves
+        layout_checks.equal_balance(s.layout_entries, (mx, mean, per), s.layout_waves)
 
 
 def test_overlap_full_grid_launches(gpu, nat, monkeypatch):
@@ -193,3 +172,31 @@ def test_halo_choice_layout_is_a_fresh_layout(gpu, nat, monkeypatch):
     assert s2.overlap and s2.ti == ti
     assert s2.layout_boundary == nb1
     assert [tuple(e) for e in s2.layout_entries] == ent1
+
+
+@pytest.mark.parametrize("case", ["equal-64", "4x2-overlap", "fused-order3"])
+def test_live_list_is_the_planners(gpu, nat, monkeypatch, case):
+    """What the device walks is what the host planner builds: item_layout()
+    called with a live solver's layout_request gives the solver's list entry
+    for entry, with its boundary count, waves and name."""
+    M = N = 2048
+    opt = nat.SolveOptions()
+    opt.check_tol = False
+    blk, comm = D.block(M, N, 1, 0), None
+    if case == "equal-64":
+        monkeypatch.setenv("PE_TI", "64")
+        monkeypatch.setenv("PE_LAYOUT", "equal")
+    elif case == "4x2-overlap":
+        monkeypatch.setenv("PE_OVERLAP", "1")
+        blk = nat.decompose(M, N, D.grid(8, M, N, "4x2"), 4)
+        comm = nat.make_delay_comm(8, 0.0, 0.0)
+    else:
+        monkeypatch.setenv("PE_ORDER", "3")
+        opt.algo = 2
+    s = nat.DeviceSolver(EllipseProblem(M, N).to_native(), blk, comm, opt)
+    assert s.overlap == (case == "4x2-overlap") and s.order == (3 if case == "fused-order3" else 0)
+    ents = [tuple(e) for e in s.layout_entries]
+    assert len(ents) > 0
+    lay = nat.item_layout(**s.layout_request)
+    assert [tuple(e) for e in lay["entries"]] == ents
+    assert lay["boundary"] == s.layout_boundary and lay["waves"] == s.layout_waves and lay["name"] == s.layout_name
