@@ -12,6 +12,7 @@ import sys
 
 import numpy as np
 import pytest
+import sweep_checks
 import torch
 
 from poisson_ellipse_openmp_mpi_cuda_amd import EllipseProblem, solve
@@ -955,33 +956,10 @@ def test_production_sweep_vs_torch_recurrence(gpu, nat, M, N, kernel, monkeypatc
     planes and w against torch_ref.single_sweep (reference operator,
     divisions; the kernels use the division-free coefficient path) —
     reference iteration: stage2-mpi/poisson_mpi_decomp.cpp:400-457."""
-    K = 20
     monkeypatch.setenv("PE_RESIDENT", "1" if kernel == "resident" else "0")
-    prob = EllipseProblem(M, N)
-    opt = nat.SolveOptions()
-    opt.algo = 2
-    opt.check_tol = False
-    s = nat.DeviceSolver(prob.to_native(), D.block(M, N, 1, 0), None, opt)
+    s = sweep_checks.solver(nat, M, N, "single")
     assert s.resident == (kernel == "resident")
-    s.reset()
-    s.run_iterations(K, False)
-    s.synchronize()
-    st = s.state()
-    ref = torch_ref.single_sweep(prob, K)
-    par = (K - 1) & 1
-    got, want = st["fs"][par], ref.sums[K]
-    scale = max(abs(x) for x in want)
-    for n in range(7):
-        assert got[n] == pytest.approx(want[n], rel=1e-10, abs=1e-13 * scale), n
-    assert st["alpha"] == pytest.approx(ref.alpha[-1], rel=1e-12)
-    assert st["beta"] == pytest.approx(ref.beta[-1], rel=1e-12)
-    fields = {"r": s.field(0 if par == 0 else 4), "p": s.field(2 if par == 0 else 3)}
-    for name, f in fields.items():
-        want_f = getattr(ref, name)[1:M, 1:N].numpy()
-        np.testing.assert_allclose(f[2:M + 1, 2:N + 1], want_f, rtol=0, atol=1e-12 * np.abs(want_f).max(),
-                                   err_msg=name)
-    wref = ref.w[1:M, 1:N].numpy()
-    np.testing.assert_allclose(s.w(), wref, rtol=0, atol=1e-12 * np.abs(wref).max())
+    sweep_checks.check_sweeps(s, M, N, "single", 20)  # (sums rel 1e-10, α β and the planes 1e-12)
 
 
 def test_virtual_split_sweep_vs_torch_recurrence(gpu):

@@ -14,6 +14,7 @@ import os
 
 import numpy as np
 import pytest
+import sweep_checks
 
 from poisson_ellipse_openmp_mpi_cuda_amd import EllipseProblem, solve
 from poisson_ellipse_openmp_mpi_cuda_amd.models.ellipse import GOLDEN_ITERS, GOLDEN_L2
@@ -58,30 +59,9 @@ def test_three_step_sweeps_vs_torch_recurrence(gpu, nat, M, N):
     reduced sums, α₃, β₃, the r / p planes and w against torch_ref.three_step
     (reference operator, divisions; the kernel uses the division-free
     coefficients)."""
-    J = 8
-    prob = EllipseProblem(M, N)
-    s = _solver(nat, prob)
+    s = sweep_checks.solver(nat, M, N, "three")
     assert s.sweep_steps == 3
-    s.reset()
-    s.run_iterations(3 * J, False)
-    s.synchronize()
-    st = s.state()
-    assert st["iter"] == 3 * J and st["status"] == 0
-    ref = torch_ref.three_step(prob, J)
-    par = (J - 1) & 1
-    got, want = st["fs2"][par], ref.sums[J]
-    scale = max(abs(x) for x in want)
-    for n in range(19):
-        assert got[n] == pytest.approx(want[n], rel=1e-9, abs=1e-12 * scale), n
-    assert st["alpha"] == pytest.approx(ref.alpha[-1][2], rel=1e-11)
-    assert st["beta"] == pytest.approx(ref.beta[-1][2], rel=1e-11)
-    fields = {"r": s.field(0 if par == 0 else 4), "p": s.field(2 if par == 0 else 3)}
-    for name, f in fields.items():
-        want_f = getattr(ref, name)[1:M, 1:N].numpy()
-        np.testing.assert_allclose(f[2:M + 1, 2:N + 1], want_f, rtol=0, atol=1e-11 * np.abs(want_f).max(),
-                                   err_msg=name)
-    wref = ref.w[1:M, 1:N].numpy()
-    np.testing.assert_allclose(s.w(), wref, rtol=0, atol=1e-11 * np.abs(wref).max())
+    sweep_checks.check_sweeps(s, M, N, "three", 8)  # (sums rel 1e-9, α β and the planes 1e-11)
 
 
 @pytest.mark.parametrize("n", [1, 2, 4, 20, 23])

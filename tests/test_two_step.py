@@ -12,10 +12,10 @@ import os
 
 import numpy as np
 import pytest
+import sweep_checks
 
 from poisson_ellipse_openmp_mpi_cuda_amd import EllipseProblem, solve
 from poisson_ellipse_openmp_mpi_cuda_amd.models.ellipse import GOLDEN_ITERS, GOLDEN_L2
-from poisson_ellipse_openmp_mpi_cuda_amd.ops import torch_ref
 from poisson_ellipse_openmp_mpi_cuda_amd.parallel import decomp as D
 
 pytestmark = pytest.mark.gpu
@@ -46,33 +46,9 @@ def test_two_step_sweeps_vs_torch_recurrence(gpu, nat, M, N):
     reduced sums, α₂, β₂, the r / p planes and w against torch_ref.two_step
     (reference operator, divisions; the kernel uses the division-free
     coefficients)."""
-    J = 10
-    prob = EllipseProblem(M, N)
-    opt = nat.SolveOptions()
-    opt.algo = 3
-    opt.check_tol = False
-    s = nat.DeviceSolver(prob.to_native(), D.block(M, N, 1, 0), None, opt)
+    s = sweep_checks.solver(nat, M, N, "two")
     assert s.two_step
-    s.reset()
-    s.run_iterations(2 * J, False)
-    s.synchronize()
-    st = s.state()
-    assert st["iter"] == 2 * J and st["status"] == 0
-    ref = torch_ref.two_step(prob, J)
-    par = (J - 1) & 1
-    got, want = st["fs2"][par], ref.sums[J]
-    scale = max(abs(x) for x in want)
-    for n in range(20):
-        assert got[n] == pytest.approx(want[n], rel=1e-9, abs=1e-12 * scale), n
-    assert st["alpha"] == pytest.approx(ref.alpha[-1][1], rel=1e-11)
-    assert st["beta"] == pytest.approx(ref.beta[-1][1], rel=1e-11)
-    fields = {"r": s.field(0 if par == 0 else 4), "p": s.field(2 if par == 0 else 3)}
-    for name, f in fields.items():
-        want_f = getattr(ref, name)[1:M, 1:N].numpy()
-        np.testing.assert_allclose(f[2:M + 1, 2:N + 1], want_f, rtol=0, atol=1e-11 * np.abs(want_f).max(),
-                                   err_msg=name)
-    wref = ref.w[1:M, 1:N].numpy()
-    np.testing.assert_allclose(s.w(), wref, rtol=0, atol=1e-11 * np.abs(wref).max())
+    sweep_checks.check_sweeps(s, M, N, "two", 10)  # (sums rel 1e-9, α β and the planes 1e-11)
 
 
 @pytest.mark.parametrize("M,N", [(40, 40), (400, 600), (800, 1200), (257, 129)])
