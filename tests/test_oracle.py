@@ -2,6 +2,7 @@
 on-the-fly coefficient path (chord tables + per-row classes, host mirror)
 vs the oracle's fic_reg assembly — bit-for-bit."""
 
+import halo_checks
 import numpy as np
 import pytest
 import sweep_checks
@@ -157,3 +158,38 @@ def test_edge_shape_references_agree(kind, M, N, count):
     ref = torch_ref.pcg(prob, max_iter=K)
     assert ref.iters == K and not ref.converged
     assert float((one.w - ref.w).abs().max()) <= 1e-13 * float(ref.w.abs().max())
+
+
+@pytest.mark.parametrize("kind,M,N,K", halo_checks.REFERENCE_CASES)
+def test_halo_case_references_agree(kind, M, N, K):
+    """The references of the multi-rank cases (halo_checks), at their iteration
+    counts: the reference PCG loop capped at K ends there unconverged, the
+    single sweep — what the cases are compared with — equals it to 1e-13 of
+    the maximum on w, and where K is whole sweeps the kind's multi-step
+    recurrence equals the single sweep to 1e-11 on w, r and p.  (The shapes
+    converge in 29 to 148 iterations; single sweep vs PCG at most 1.7e-15,
+    multi-step vs single sweep at most 3.3e-13: each at least 30 times inside
+    the kernels' bounds.)"""
+    steps = sweep_checks.KINDS[kind][1]
+    prob = EllipseProblem(M, N)
+    one = sweep_checks.reference("single", M, N, K)
+    ref = torch_ref.pcg(prob, max_iter=K)
+    assert ref.iters == K and not ref.converged
+    assert float((one.w - ref.w).abs().max()) <= 1e-13 * float(ref.w.abs().max())
+    if steps > 1 and K % steps == 0:
+        multi = sweep_checks.reference(kind, M, N, K // steps)
+        for name in ("w", "r", "p"):
+            a, b = getattr(multi, name), getattr(one, name)
+            assert float((a - b).abs().max()) <= 1e-11 * float(b.abs().max()), name
+
+
+@pytest.mark.parametrize("M,N,ranks,decomp", sorted(halo_checks.BLOCKS))
+def test_halo_case_blocks(M, N, ranks, decomp):
+    """The decomposition gives the multi-rank cases the block sizes they are
+    there for (slabs of 8, 12/11/11/11, 13/12/12 rows, blocks of 12×12, ...)."""
+    rows, cols = halo_checks.BLOCKS[(M, N, ranks, decomp)]
+    blks = D.blocks(M, N, ranks, decomp)
+    assert (blks[0].Px, blks[0].Py) == (len(rows), len(cols))
+    assert sorted({(b.i0, b.nx) for b in blks}) == [(1 + sum(rows[:i]), rows[i]) for i in range(len(rows))]
+    assert sorted({(b.j0, b.ny) for b in blks}) == [(1 + sum(cols[:j]), cols[j]) for j in range(len(cols))]
+    assert sum(rows) == M - 1 and sum(cols) == N - 1
