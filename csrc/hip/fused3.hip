@@ -416,6 +416,26 @@ struct M3Rings {
   bool pushed;
 };
 
+// Row addresses of the steady groups: one 64-bit byte base per stream in
+// SGPRs, advanced by the stream's row pitch once per row step, and
+// loop-invariant 32-bit byte offsets per lane (global_load / global_store's
+// SGPR base + VGPR offset form) — no 64-bit row·pitch product per access.
+// The w rows stored (t-2) and loaded (t-2+WD) share a base: the WD rows
+// between them are part of the load's lane offset.  Offsets stay inside
+// 1 + WD rows (< 4 GiB by far); the bases carry the plane offsets past it.
+// (Global address space by type: the bases pass through an empty asm every
+// step, behind which the compiler no longer sees that they point to global
+// memory and falls back to flat accesses with 64-bit lane addresses.)
+typedef __attribute__((address_space(1))) char gchar3;
+typedef __attribute__((address_space(1))) double gdouble3;
+struct M3Ptr {
+  const gchar3* xi;  // input row t + XD (r plane; the p plane is poff further)
+  gchar3* yo;        // output row t - 3
+  gchar3* wo;        // w row t - 2
+  unsigned pb, wb;              // row pitches of x and w, bytes
+  unsigned roff, poffb, wloff;  // lane offsets: r plane / w, p plane, w load
+};
+
 // A wave's first item as loaded at kernel entry: its list entry and the
 // row-class entry of its first row window — the two dependent loads in front
 // of its first row loads.  Neither depends on the sweep's scalars, so their
@@ -458,6 +478,27 @@ __device__ __forceinline__ double ldx3(const KParams& k, const M3Ctx& c, int t, 
 #endif
 }
 
+// A row load through a uniform byte base and a 32-bit lane offset.
+// (The empty asm keeps the offset's zero-extension next to the access: hoisted
+// out of the loop as a 64-bit lane value it costs a v_lshl_add_u64 per access
+// instead of the SGPR-base addressing mode.  In place, so no copy is made.)
+__device__ __forceinline__ double ldxb3(const gchar3* base, unsigned& off) {
+  asm("" : "+v"(off));
+#if PE_S3_NTX
+  return __builtin_nontemporal_load(reinterpret_cast<const gdouble3*>(base + off));
+#else
+  return *reinterpret_cast<const gdouble3*>(base + off);
+#endif
+}
+__device__ __forceinline__ double ldntb3(const gchar3* base, unsigned& off) {
+  asm("" : "+v"(off));
+  return __builtin_nontemporal_load(reinterpret_cast<const gdouble3*>(base + off));
+}
+__device__ __forceinline__ void stntb3(gchar3* base, unsigned& off, double v) {
+  asm("" : "+v"(off));
+  __builtin_nontemporal_store(v, reinterpret_cast<gdouble3*>(base + off));
+}
+
 __device__ __forceinline__ double ldnt1(const double* p) { return __builtin_nontemporal_load(p); }
 __device__ __forceinline__ void stnt1(double* p, double v) { __builtin_nontemporal_store(v, p); }
 
@@ -480,8 +521,8 @@ __device__ __forceinline__ void push_row3(const KParams& k, const M3Ctx& c, M3Ri
 // is the band face-ring slot of row t.  STEADY (uniform items): every stage
 // row lies inside the item — no row tests, no clamped loads.
 template <int KIND, bool PUSH, bool EDGE, bool STEADY, int JJ>
-__device__ __forceinline__ void step3(const KParams& k, const M3Ctx& c, M3Rings& x, const RowCtx& rx, WaveTV3& tvw,
-                                      double (&sv)[NS], int n, int bs) {
+__device__ __forceinline__ void step3(const KParams& k, const M3Ctx& c, M3Rings& x, M3Ptr& rp, const RowCtx& rx,
+                                      WaveTV3& tvw, double (&sv)[NS], int n, int bs) {
   constexpr bool BAND = KIND == kBand, UNI = KIND == kUniform;
   constexpr int XD = kS3XD, WD = kS3WD;
   const double zc1 = c.zc1, zc2 = c.zc2, zc3 = c.zc3, w1 = c.w1, w2 = c.w2, w3 = c.w3;
@@ -532,11 +573,21 @@ __device__ __forceinline__ void step3(const KParams& k, const M3Ctx& c, M3Rings&
   };
   // ---- A: row t ----
   const double rin = x.RQ[xs], pin = x.PQ[xs], wrow = x.WQ[ws];
-  {
-    const int tn = STEADY ? t + XD : min(t + XD, c.tmax);
+  if constexpr (STEADY) {  // running row pointers (M3Ptr); PUSH: the halo rows keep their own formula
+    const int tn = t + XD;
+    if (PUSH && ((tn < 1 && k.has[LEFT]) || (tn > c.nx && k.has[RIGHT]))) {
+      x.RQ[xs] = ldx3<PUSH>(k, c, tn, c.off);
+      x.PQ[xs] = ldx3<PUSH>(k, c, tn, unsigned(c.poff) + c.off);
+    } else {
+      x.RQ[xs] = ldxb3(rp.xi, rp.roff);
+      x.PQ[xs] = ldxb3(rp.xi, rp.poffb);
+    }
+    x.WQ[ws] = c.o0 ? ldntb3(rp.wo, rp.wloff) : 0.0;
+  } else {
+    const int tn = min(t + XD, c.tmax);
     x.RQ[xs] = ldx3<PUSH>(k, c, tn, c.off);
     x.PQ[xs] = ldx3<PUSH>(k, c, tn, unsigned(c.poff) + c.off);
-    const int wr = STEADY ? t - 2 + WD : min(max(t - 2 + WD, c.ib), c.ie);
+    const int wr = min(max(t - 2 + WD, c.ib), c.ie);
     // (only the lanes that store w load it: the 12 halo lanes' columns are a
     // neighbouring strip's, and their lines would be fetched for nothing)
     x.WQ[ws] = c.o0 ? ldnt1(c.Wm + int64_t(wr) * c.wp + c.off) : 0.0;
@@ -574,7 +625,11 @@ __device__ __forceinline__ void step3(const KParams& k, const M3Ctx& c, M3Rings&
     x.R2[e0] = r2;
     const double p3 = zc3 * z + c.b3 * p2;
     x.P3[m2] = p3;
-    if (own(q) && c.o0) stnt1(c.Wm + int64_t(q) * c.wp + c.off, wrow + w1 * x.P1[m2] + w2 * p2 + w3 * p3);
+    if (own(q) && c.o0) {
+      const double wn = wrow + w1 * x.P1[m2] + w2 * p2 + w3 * p3;
+      if constexpr (STEADY) stntb3(rp.wo, rp.roff, wn);
+      else stnt1(c.Wm + int64_t(q) * c.wp + c.off, wn);
+    }
     if (inr(q)) put(17, p2 * p2);
   }
   if (STEADY) __builtin_amdgcn_sched_barrier(0);
@@ -590,9 +645,14 @@ __device__ __forceinline__ void step3(const KParams& k, const M3Ctx& c, M3Rings&
     const double p3 = x.P3[m0];
     if (own(q) && !c.fix) {
       if (c.o0) {
-        double* yr = c.Ym + int64_t(q) * c.pitch + c.off;
-        stnt1(yr, r3);
-        stnt1(yr + c.poff, p3);
+        if constexpr (STEADY) {
+          stntb3(rp.yo, rp.roff, r3);
+          stntb3(rp.yo, rp.poffb, p3);
+        } else {
+          double* yr = c.Ym + int64_t(q) * c.pitch + c.off;
+          stnt1(yr, r3);
+          stnt1(yr + c.poff, p3);
+        }
       }
       if constexpr (PUSH) push_row3(k, c, x, q, r3, p3);
     }
@@ -656,6 +716,13 @@ __device__ __forceinline__ void step3(const KParams& k, const M3Ctx& c, M3Rings&
       put(15, vv * avv);  // (ṽ,Aṽ)
     }
   }
+  if constexpr (STEADY) {  // next row: one 64-bit add per stream
+    rp.xi += rp.pb;
+    rp.yo += rp.pb;
+    rp.wo += rp.wb;
+    // (opaque: the six steps' bases are not re-derived as base + JJ·pitch)
+    asm("" : "+s"(rp.xi), "+s"(rp.yo), "+s"(rp.wo));
+  }
 }
 
 // Six row steps (one period of the register rings).  Generic groups stop at
@@ -663,12 +730,12 @@ __device__ __forceinline__ void step3(const KParams& k, const M3Ctx& c, M3Rings&
 // barrier after each step keeps the scheduler from hoisting later steps'
 // work into this one.
 template <int KIND, bool PUSH, bool EDGE, bool STEADY>
-__device__ __forceinline__ void group3(const KParams& k, const M3Ctx& c, M3Rings& x, const RowCtx& rx, WaveTV3& tvw,
-                                       double (&sv)[NS], int n0, int nsteps, int& bs) {
+__device__ __forceinline__ void group3(const KParams& k, const M3Ctx& c, M3Rings& x, M3Ptr& rp, const RowCtx& rx,
+                                       WaveTV3& tvw, double (&sv)[NS], int n0, int nsteps, int& bs) {
   auto adv = [&]() { bs = bs == kRing3 - 1 ? 0 : bs + 1; };
 #define PE_STEP3(JJ)                                                              \
   if (STEADY || n0 + JJ < nsteps) {                                               \
-    step3<KIND, PUSH, EDGE, STEADY, JJ>(k, c, x, rx, tvw, sv, n0 + JJ, bs);       \
+    step3<KIND, PUSH, EDGE, STEADY, JJ>(k, c, x, rp, rx, tvw, sv, n0 + JJ, bs);   \
     adv();                                                                        \
     if (STEADY) __builtin_amdgcn_sched_barrier(0);                                \
   }
@@ -764,6 +831,11 @@ __device__ __forceinline__ void march3(const KParams& k, const Coef3& cf, bool f
   c.w1 = cf.cw[0];
   c.w2 = cf.cw[1];
   c.w3 = cf.cw[2];
+  // (w's three coefficients live in VGPRs: the march has ~25 to spare and no
+  // SGPRs — as scalars they were spilled and reloaded by v_readlane in every
+  // row step, with a wait state before each use; moving more of the twelve
+  // only moved the spills to other scalars)
+  asm("" : "+v"(c.w1), "+v"(c.w2), "+v"(c.w3));
 
   // Row classes / column tables of a 64-row window, reloaded every ~58 rows
   // on tall items (stage rows t-6 .. t and the column-table row t+1 inside).
@@ -825,22 +897,34 @@ __device__ __forceinline__ void march3(const KParams& k, const Coef3& cf, bool f
   auto reload = [&](int n0) {
     if (c.t0 + n0 + 6 - rx.segbase > 63) load_seg(c.t0 + n0 - H3);  // tall items: next row window
   };
+  M3Ptr rp;
+  rp.pb = unsigned(c.pitch) * 8u;
+  rp.wb = unsigned(c.wp) * 8u;
+  rp.roff = c.off * 8u;
+  rp.poffb = (unsigned(c.poff) + c.off) * 8u;
+  rp.wloff = rp.roff + unsigned(WD) * rp.wb;
+  rp.xi = nullptr;
+  rp.yo = rp.wo = nullptr;
   int n0 = 0;
   const int nsteady_end = KIND == kUniform ? rows + 4 - 5 : -1;  // last steady group start
   for (; n0 < nsteps && !(n0 >= 12 && n0 <= nsteady_end); n0 += 6) {
     reload(n0);
-    group3<KIND, PUSH, EDGE, false>(k, c, x, rx, tvw, sv, n0, nsteps, bs);
+    group3<KIND, PUSH, EDGE, false>(k, c, x, rp, rx, tvw, sv, n0, nsteps, bs);
     sstamp();
   }
   if constexpr (KIND == kUniform) {
+    // the steady groups' row bases, at the first steady step's rows
+    rp.xi = (const gchar3*)(c.Xm + int64_t(c.t0 + n0 + XD) * c.pitch);
+    rp.yo = (gchar3*)(c.Ym + int64_t(c.t0 + n0 - 3) * c.pitch);
+    rp.wo = (gchar3*)(c.Wm + int64_t(c.t0 + n0 - 2) * c.wp);
     for (; n0 <= nsteady_end; n0 += 6) {
       reload(n0);
-      group3<KIND, PUSH, EDGE, true>(k, c, x, rx, tvw, sv, n0, nsteps, bs);
+      group3<KIND, PUSH, EDGE, true>(k, c, x, rp, rx, tvw, sv, n0, nsteps, bs);
       sstamp();
     }
     for (; n0 < nsteps; n0 += 6) {
       reload(n0);
-      group3<KIND, PUSH, EDGE, false>(k, c, x, rx, tvw, sv, n0, nsteps, bs);
+      group3<KIND, PUSH, EDGE, false>(k, c, x, rp, rx, tvw, sv, n0, nsteps, bs);
       sstamp();
     }
   }
