@@ -87,6 +87,23 @@ py::dict state_dict(const dev::DevState& s) {
   return d;
 }
 
+// User fields from Python: None or a float64 array of the given shape (any
+// layout / dtype numpy converts; the Python layer rejects lossy conversions
+// and non-finite values first).  `hold` keeps the converted array alive.
+using FieldArr = py::array_t<double, py::array::c_style | py::array::forcecast>;
+const double* field_ptr(const py::object& o, int64_t rows, int64_t cols, const char* name, FieldArr& hold) {
+  if (o.is_none()) return nullptr;
+  hold = FieldArr::ensure(o);
+  if (!hold) {
+    PyErr_Clear();
+    throw std::invalid_argument(std::string(name) + ": not convertible to a float64 array");
+  }
+  if (hold.ndim() != 2 || hold.shape(0) != rows || hold.shape(1) != cols)
+    throw std::invalid_argument(std::string(name) + ": expected shape (" + std::to_string(rows) + ", " +
+                                std::to_string(cols) + ")");
+  return hold.data();
+}
+
 // Handle to a DeviceComm owned by Python.
 struct CommHandle {
   std::unique_ptr<DeviceComm> comm;
@@ -224,18 +241,24 @@ PYBIND11_MODULE(_native, m) {
       py::arg("return_w") = false);
   m.def(
       "cpu_solve_grid",
-      [](const Problem& P, const ProcessGrid& pg, const SolveOptions& opt, bool return_w) {
+      [](const Problem& P, const ProcessGrid& pg, const SolveOptions& opt, bool return_w, py::object rhs,
+         py::object w0) {
+        FieldArr hr, hw;
+        UserFields uf;
+        uf.rhs = field_ptr(rhs, P.M - 1, P.N - 1, "rhs", hr);
+        uf.w0 = field_ptr(w0, P.M - 1, P.N - 1, "w0", hw);
         std::vector<double> w;
         SolveResult r;
         {
           py::gil_scoped_release nogil;
-          r = cpu_pcg_threads(P, pg, opt, return_w ? &w : nullptr);
+          r = cpu_pcg_threads(P, pg, opt, return_w ? &w : nullptr, uf);
         }
         py::object wa = py::none();
         if (return_w) wa = to_array(std::move(w), P.M - 1, P.N - 1);
         return py::make_tuple(r, wa);
       },
-      py::arg("prob"), py::arg("grid"), py::arg("opt") = SolveOptions(), py::arg("return_w") = false);
+      py::arg("prob"), py::arg("grid"), py::arg("opt") = SolveOptions(), py::arg("return_w") = false,
+      py::arg("rhs") = py::none(), py::arg("w0") = py::none());
 
   // One rank of a multi-process CPU run; the transport is Python callbacks
   // (torch.distributed, typically gloo).  exchange_fn receives a list of
@@ -243,7 +266,11 @@ PYBIND11_MODULE(_native, m) {
   m.def(
       "cpu_solve_rank",
       [](const Problem& P, const Block& blk, py::function reduce_fn, py::function exchange_fn,
-         py::function barrier_fn, const SolveOptions& opt, bool return_w) {
+         py::function barrier_fn, const SolveOptions& opt, bool return_w, py::object rhs, py::object w0) {
+        FieldArr hr, hw;
+        UserFields uf;  // the GLOBAL arrays: every rank passes the same and takes its slice
+        uf.rhs = field_ptr(rhs, P.M - 1, P.N - 1, "rhs", hr);
+        uf.w0 = field_ptr(w0, P.M - 1, P.N - 1, "w0", hw);
         auto reduce = [reduce_fn](double* buf, int n, bool is_max) {
           py::gil_scoped_acquire g;
           py::array_t<double> a({n}, {int64_t(sizeof(double))}, buf, py::none());
@@ -268,14 +295,31 @@ PYBIND11_MODULE(_native, m) {
         SolveResult r;
         {
           py::gil_scoped_release nogil;
-          r = cpu_pcg(P, blk, comm, opt, return_w ? &w : nullptr);
+          r = cpu_pcg(P, blk, comm, opt, return_w ? &w : nullptr, uf);
         }
         py::object wa = py::none();
         if (return_w) wa = to_array(std::move(w), blk.nx, blk.ny);
         return py::make_tuple(r, wa);
       },
       py::arg("prob"), py::arg("block"), py::arg("reduce_fn"), py::arg("exchange_fn"), py::arg("barrier_fn"),
-      py::arg("opt") = SolveOptions(), py::arg("return_w") = false);
+      py::arg("opt") = SolveOptions(), py::arg("return_w") = false, py::arg("rhs") = py::none(),
+      py::arg("w0") = py::none());
+
+  // One block's slices of global interior arrays (pe/fields.hpp block_field):
+  // (rhs owned nx × ny | None, w0 with its ring (nx+2) × (ny+2) | None) — the
+  // operands of DeviceSolver.set_rhs / set_w0.
+  m.def(
+      "block_fields",
+      [](int M, int N, const Block& blk, py::object rhs, py::object w0) {
+        FieldArr hr, hw;
+        const double* r = field_ptr(rhs, int64_t(M) - 1, int64_t(N) - 1, "rhs", hr);
+        const double* w = field_ptr(w0, int64_t(M) - 1, int64_t(N) - 1, "w0", hw);
+        py::object ro = py::none(), wo = py::none();
+        if (r) ro = to_array(block_field(r, M, N, blk, 0), blk.nx, blk.ny);
+        if (w) wo = to_array(block_field(w, M, N, blk, 1), blk.nx + 2, blk.ny + 2);
+        return py::make_tuple(ro, wo);
+      },
+      py::arg("M"), py::arg("N"), py::arg("block"), py::arg("rhs") = py::none(), py::arg("w0") = py::none());
 
   m.def("host_coefficients", [](const Problem& P, const Block& blk) {
     std::vector<double> a, b;
@@ -482,6 +526,23 @@ PYBIND11_MODULE(_native, m) {
            py::arg("iters"), py::arg("use_graph") = true)
       .def("set_check_tol", &DeviceSolver::set_check_tol, py::arg("on"))
       .def("set_init", &DeviceSolver::set_init, py::arg("init"), py::arg("seed") = 1234, py::arg("amp") = 0.05)
+      .def(
+          "set_rhs",
+          [](DeviceSolver& s, py::object owned) {
+            FieldArr h;
+            s.set_rhs(field_ptr(owned, s.block().nx, s.block().ny, "rhs", h));
+          },
+          py::arg("owned"), "this block's nx × ny slice of the right-hand side (block_fields), or None for F")
+      .def(
+          "set_w0",
+          [](DeviceSolver& s, py::object ringed) {
+            FieldArr h;
+            s.set_w0(field_ptr(ringed, s.block().nx + 2, s.block().ny + 2, "w0", h));
+          },
+          py::arg("ringed"),
+          "this block's (nx+2) × (ny+2) slice of the initial guess with its ring (block_fields), or None for init")
+      .def_property_readonly("user_rhs", &DeviceSolver::user_rhs)
+      .def_property_readonly("user_w0", &DeviceSolver::user_w0)
       .def("relayout", &DeviceSolver::relayout, py::arg("ti"), py::arg("order") = -1)
       .def("prepare_graphs",
            [](DeviceSolver& s, int64_t n) {
@@ -627,18 +688,24 @@ PYBIND11_MODULE(_native, m) {
 
   m.def(
       "device_solve_group_grid",
-      [](const Problem& P, const ProcessGrid& pg, const SolveOptions& opt, bool return_w) {
+      [](const Problem& P, const ProcessGrid& pg, const SolveOptions& opt, bool return_w, py::object rhs,
+         py::object w0) {
+        FieldArr hr, hw;
+        UserFields uf;
+        uf.rhs = field_ptr(rhs, P.M - 1, P.N - 1, "rhs", hr);
+        uf.w0 = field_ptr(w0, P.M - 1, P.N - 1, "w0", hw);
         std::vector<double> w;
         SolveResult r;
         {
           py::gil_scoped_release nogil;
-          r = device_solve_group(P, pg, opt, return_w ? &w : nullptr);
+          r = device_solve_group(P, pg, opt, return_w ? &w : nullptr, uf);
         }
         py::object wa = py::none();
         if (return_w) wa = to_array(std::move(w), P.M - 1, P.N - 1);
         return py::make_tuple(r, wa);
       },
-      py::arg("prob"), py::arg("grid"), py::arg("opt") = SolveOptions(), py::arg("return_w") = false);
+      py::arg("prob"), py::arg("grid"), py::arg("opt") = SolveOptions(), py::arg("return_w") = false,
+      py::arg("rhs") = py::none(), py::arg("w0") = py::none());
 
   // Single-shot device ops for numerics tests: `p` is a full local field
   // (rows × pitch, halo included); returns arrays of the same shape.

@@ -64,7 +64,8 @@ double row_sum(const Block& blk, int T, F&& term) {
   return s;
 }
 
-void assemble(const Problem& P, const Block& blk, Fields& f, int T) {
+// `rhs`: the block's owned nx × ny share of a user right-hand side (null: F).
+void assemble(const Problem& P, const Block& blk, Fields& f, int T, const double* rhs) {
   const double h1 = P.h1(), h2 = P.h2(), eps = P.eps();
   // a, b on the block plus a 1-wide ring (reference :132-157).
 #pragma omp parallel for schedule(static) num_threads(T) if (T > 1)
@@ -86,7 +87,8 @@ void assemble(const Problem& P, const Block& blk, Fields& f, int T) {
     const double x = P.A1 + (blk.i0 - 1 + li) * h1;
     for (int64_t lj = 1; lj <= blk.ny; ++lj) {
       const double y = P.A2 + (blk.j0 - 1 + lj) * h2;
-      f.B[blk.at(li, lj)] = in_ellipse(x, y, P.cx, P.cy) ? P.F : 0.0;
+      const double Fij = rhs ? rhs[(li - 1) * blk.ny + (lj - 1)] : P.F;
+      f.B[blk.at(li, lj)] = in_ellipse(x, y, P.cx, P.cy) ? Fij : 0.0;
     }
   }
 }
@@ -175,7 +177,7 @@ class HaloExchanger {
 }  // namespace
 
 SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const SolveOptions& opt,
-                    std::vector<double>* w_out) {
+                    std::vector<double>* w_out, const UserFields& uf) {
   const auto t_start = clk::now();
   SolveResult res;
   res.backend = opt.threads > 1 ? "cpu-omp" : "cpu-serial";
@@ -187,14 +189,25 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
   const int64_t max_iter = P.iter_cap();
 
   Fields f(blk.alloc);
-  assemble(P, blk, f, T);
+  {
+    std::vector<double> rhs;
+    if (uf.rhs) rhs = block_field(uf.rhs, P.M, P.N, blk, 0);
+    assemble(P, blk, f, T, uf.rhs ? rhs.data() : nullptr);
+  }
   HaloExchanger halo(blk);
 
-  // Initial guess: w⁰ = 0 (reference :384) or a deterministic random field.
-  if (opt.init == Init::Random) {
-    for (int64_t li = 0; li <= blk.nx + 1; ++li)
-      for (int64_t lj = 0; lj <= blk.ny + 1; ++lj)
-        f.w[blk.at(li, lj)] = random_w0(blk.i0 - 1 + li, blk.j0 - 1 + lj, P.M, P.N, opt.seed, opt.init_amp);
+  // Initial guess: w⁰ = 0 (reference :384), a deterministic random field, or
+  // the user's (its ring travels with the slice: no exchange before r⁰).
+  if (uf.w0 || opt.init == Init::Random) {
+    if (uf.w0) {
+      const std::vector<double> w0 = block_field(uf.w0, P.M, P.N, blk, 1);
+      for (int64_t li = 0; li <= blk.nx + 1; ++li)
+        for (int64_t lj = 0; lj <= blk.ny + 1; ++lj) f.w[blk.at(li, lj)] = w0[size_t(li * (blk.ny + 2) + lj)];
+    } else {
+      for (int64_t li = 0; li <= blk.nx + 1; ++li)
+        for (int64_t lj = 0; lj <= blk.ny + 1; ++lj)
+          f.w[blk.at(li, lj)] = random_w0(blk.i0 - 1 + li, blk.j0 - 1 + lj, P.M, P.N, opt.seed, opt.init_amp);
+    }
     apply_A(blk, f.w.data(), f.a.data(), f.b.data(), f.Ap.data(), h1, h2, T);
     for (int64_t li = 1; li <= blk.nx; ++li)
       for (int64_t lj = 1; lj <= blk.ny; ++lj) {
@@ -333,8 +346,9 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
     }
     comm.allreduce_sum(acc, 1);
     comm.allreduce_max(mx, 2);
-    res.l2_err = std::sqrt(acc[0] * h1 * h2);
-    res.max_err = mx[0];
+    // (a user right-hand side has no analytic solution here: -1)
+    res.l2_err = uf.rhs ? -1.0 : std::sqrt(acc[0] * h1 * h2);
+    res.max_err = uf.rhs ? -1.0 : mx[0];
     res.max_outside = mx[1];
   }
   if (w_out) {
@@ -348,12 +362,12 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
 }
 
 SolveResult cpu_pcg_threads(const Problem& P, int ranks, DecompMode mode, const SolveOptions& opt,
-                            std::vector<double>* w_out) {
-  return cpu_pcg_threads(P, choose_process_grid(ranks, P.M, P.N, mode), opt, w_out);
+                            std::vector<double>* w_out, const UserFields& uf) {
+  return cpu_pcg_threads(P, choose_process_grid(ranks, P.M, P.N, mode), opt, w_out, uf);
 }
 
 SolveResult cpu_pcg_threads(const Problem& P, const ProcessGrid& pg, const SolveOptions& opt,
-                            std::vector<double>* w_out) {
+                            std::vector<double>* w_out, const UserFields& uf) {
   const int ranks = pg.Px * pg.Py;
   auto group = make_thread_group(ranks);
   std::vector<SolveResult> results(ranks);
@@ -366,7 +380,7 @@ SolveResult cpu_pcg_threads(const Problem& P, const ProcessGrid& pg, const Solve
     th.emplace_back([&, r] {
       try {
         auto comm = make_thread_comm(group, r);
-        results[r] = cpu_pcg(P, blks[r], *comm, opt, w_out ? &blocks[r] : nullptr);
+        results[r] = cpu_pcg(P, blks[r], *comm, opt, w_out ? &blocks[r] : nullptr, uf);
       } catch (...) {
         errs[r] = std::current_exception();
       }

@@ -556,6 +556,25 @@ void DeviceSolver::set_init(Init init, uint64_t seed, double amp) {
   opt_.init_amp = amp;
 }
 
+void DeviceSolver::set_plane(double** plane, const double* host, int64_t n) {
+  for (auto& g : graphs_) PE_HIP_CHECK(hipGraphExecDestroy(g.second));
+  graphs_.clear();
+  if (!host) {
+    if (*plane) {
+      PE_HIP_CHECK(hipStreamSynchronize(stream_));  // (a kernel of the last solve may still read it)
+      PE_HIP_CHECK(hipFree(*plane));
+      *plane = nullptr;
+    }
+    return;
+  }
+  if (!*plane) PE_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(plane), sizeof(double) * size_t(n)));
+  upload(*plane, host, sizeof(double) * size_t(n));
+}
+
+void DeviceSolver::set_rhs(const double* owned) { set_plane(&rhs_dev_, owned, blk_.nx * blk_.ny); }
+
+void DeviceSolver::set_w0(const double* ringed) { set_plane(&w0_dev_, ringed, (blk_.nx + 2) * (blk_.ny + 2)); }
+
 void DeviceSolver::set_fused_fields(double* x0, double* x1, double* w) {
   KParams& k = *kp_;
   fields_ = x0;
@@ -625,6 +644,8 @@ DeviceSolver::~DeviceSolver() {
   if (put_buf_) (void)hipFree(put_buf_);
   if (put_cnt_) (void)hipFree(put_cnt_);
   if (stage_) (void)hipHostFree(stage_);
+  if (rhs_dev_) (void)hipFree(rhs_dev_);
+  if (w0_dev_) (void)hipFree(w0_dev_);
   (void)hipFree(partial_);
   if (hist_) (void)hipFree(hist_);
   if (stamps_) (void)hipFree(stamps_);
@@ -764,7 +785,11 @@ void DeviceSolver::enqueue_init() {
   PE_HIP_CHECK(hipMemsetAsync(halo_, 0, sizeof(double) * hsize_ * 4, stream_));
   PE_HIP_CHECK(hipMemsetAsync(st_, 0, sizeof(DevState), stream_));
   ov_epoch_ = 0;
-  dev::launch_init(*kp_, opt_.init == Init::Random ? 1 : 0, opt_.seed, opt_.init_amp, opt_.variant, stream_);
+  if (rhs_dev_ || w0_dev_)  // user fields: kInit's sibling reads B / w⁰ from the planes
+    dev::launch_init_field(*kp_, rhs_dev_, w0_dev_, opt_.init == Init::Random ? 1 : 0, opt_.seed, opt_.init_amp,
+                           opt_.variant, stream_);
+  else
+    dev::launch_init(*kp_, opt_.init == Init::Random ? 1 : 0, opt_.seed, opt_.init_amp, opt_.variant, stream_);
   PE_HIP_CHECK(hipGetLastError());
 }
 
@@ -1032,7 +1057,7 @@ void DeviceSolver::residual_pass(bool with_r, bool store) {
     dev::launch_pack(k, 0, stream_);
     enqueue_exchange(0, false);
   }
-  dev::launch_resid(k, 0, with_r, store, stream_);
+  dev::launch_resid(k, 0, with_r, store, stream_, rhs_dev_);  // (user rhs: the check and the restart's ρ are the user's problem's)
   if (comm_->size() > 1) comm_->allreduce_sum(st_->res, 4, stream_);
   PE_HIP_CHECK(hipGetLastError());
 }
@@ -1321,8 +1346,9 @@ SolveResult DeviceSolver::solve() {
   }
   res.zr = hs.rz_cur;
   if (opt_.compute_error) {
-    res.l2_err = std::sqrt(hs.err[0] * prob_.h1() * prob_.h2());
-    res.max_err = hs.err[1];
+    // (a user right-hand side has no analytic solution here: -1)
+    res.l2_err = rhs_dev_ ? -1.0 : std::sqrt(hs.err[0] * prob_.h1() * prob_.h2());
+    res.max_err = rhs_dev_ ? -1.0 : hs.err[1];
     res.max_outside = hs.err[2];
   }
   // Per-phase totals: mean per sampled live iteration (samples taken after
@@ -1418,12 +1444,12 @@ void DeviceSolver::copy_field(int which, double* host) {
 // Virtual ranks on one device.
 // ---------------------------------------------------------------------------
 SolveResult device_solve_group(const Problem& P, int ranks, DecompMode mode, const SolveOptions& opt,
-                               std::vector<double>* w_out) {
-  return device_solve_group(P, choose_process_grid(ranks, P.M, P.N, mode), opt, w_out);
+                               std::vector<double>* w_out, const UserFields& uf) {
+  return device_solve_group(P, choose_process_grid(ranks, P.M, P.N, mode), opt, w_out, uf);
 }
 
 SolveResult device_solve_group(const Problem& P, const ProcessGrid& pg, const SolveOptions& opt,
-                               std::vector<double>* w_out) {
+                               std::vector<double>* w_out, const UserFields& uf) {
   const auto t_start = clk::now();
   const int ranks = pg.Px * pg.Py;
   std::vector<std::unique_ptr<DeviceSolver>> s;
@@ -1431,6 +1457,8 @@ SolveResult device_solve_group(const Problem& P, const ProcessGrid& pg, const So
   for (int r = 0; r < ranks; ++r) {
     blks.push_back(decompose(P.M, P.N, pg, r));
     s.push_back(std::make_unique<DeviceSolver>(P, blks.back(), nullptr, opt));
+    if (uf.rhs) s.back()->set_rhs(block_field(uf.rhs, P.M, P.N, blks.back(), 0).data());
+    if (uf.w0) s.back()->set_w0(block_field(uf.w0, P.M, P.N, blks.back(), 1).data());
   }
   const bool fused = s[0]->fused();
   // multi-step sweeps (three-step on blocks of >= 12 x 12): one launch per
@@ -1561,8 +1589,8 @@ SolveResult device_solve_group(const Problem& P, const ProcessGrid& pg, const So
   res.last_diff = hs.last_diff;
   res.zr = hs.rz_cur;
   if (opt.compute_error) {
-    res.l2_err = std::sqrt(hs.err[0] * P.h1() * P.h2());
-    res.max_err = hs.err[1];
+    res.l2_err = uf.rhs ? -1.0 : std::sqrt(hs.err[0] * P.h1() * P.h2());
+    res.max_err = uf.rhs ? -1.0 : hs.err[1];
     res.max_outside = hs.err[2];
   }
   if (w_out) {

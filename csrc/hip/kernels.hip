@@ -437,6 +437,67 @@ __global__ __launch_bounds__(TJ) void kInit(KParams k, int init_random, unsigned
   }
 }
 
+// Init from user fields (DeviceSolver::set_rhs / set_w0): kInit with B read
+// from the dense nx × ny plane `Bp` (masked by the ellipse; null: F) and w⁰
+// from the dense (nx+2) × (ny+2) plane `W0` (ring = the neighbours' values,
+// 0 on the box boundary; null: kInit's zero / hash start).  Same stores (w
+// with wpitch, r with pitch into the live layout — k.r is the classic r or
+// the r-plane of x[0] behind its xorg), same sum protocol.
+template <bool EXACT>
+__global__ __launch_bounds__(TJ) void kInitField(KParams k, const double* __restrict__ Bp,
+                                                 const double* __restrict__ W0, int init_random,
+                                                 unsigned long long seed, double amp) {
+  __shared__ double sm[8];
+  __shared__ int sflag;
+  DevState* st = k.st;
+  const int64_t n = k.nx * k.ny, wc = k.ny + 2;
+  double szr = 0.0;
+  for (int64_t idx = int64_t(blockIdx.x) * TJ + threadIdx.x; idx < n; idx += int64_t(gridDim.x) * TJ) {
+    const int64_t li = idx / k.ny + 1, lj = idx % k.ny + 1;
+    const int64_t gi = k.gi0 + li, gj = k.gj0 + lj;
+    const double x = k.A1 + gi * k.h1, y = k.A2 + gj * k.h2;
+    const CS c = cset_mem<EXACT>(k, li, lj);
+    double rr = in_ellipse(x, y, k.cx, k.cy) ? (Bp ? Bp[idx] : k.F) : 0.0;
+    const int64_t at = li * k.pitch + lj;
+    if (W0) {
+      const int64_t q = li * wc + lj;
+      const double w0 = W0[q];
+      const double Aw = stencil<EXACT>(k, c, W0[q - wc], w0, W0[q + wc], W0[q - 1], W0[q + 1]);
+      rr = rr - Aw;
+      k.w[li * k.wpitch + lj] = w0;
+    } else if (init_random) {
+      const double w0 = random_w0(gi, gj, k.M, k.N, seed, amp);
+      const double Aw = stencil<EXACT>(k, c, random_w0(gi - 1, gj, k.M, k.N, seed, amp), w0,
+                                       random_w0(gi + 1, gj, k.M, k.N, seed, amp),
+                                       random_w0(gi, gj - 1, k.M, k.N, seed, amp),
+                                       random_w0(gi, gj + 1, k.M, k.N, seed, amp));
+      rr = rr - Aw;
+      k.w[li * k.wpitch + lj] = w0;
+    }
+    k.r[at] = rr;
+    if (!k.fused) {  // fused layout: launch_pack gathers the y strips
+      if (lj == 1 && k.has[DOWN]) k.send_dn[li - 1] = rr;
+      if (lj == k.ny && k.has[UP]) k.send_up[li - 1] = rr;
+    }
+    szr += zval<EXACT>(c, rr) * rr;
+  }
+  double v[1] = {szr};
+  block_reduce<1, false>(v, sm);
+  if (threadIdx.x == 0) k.partial[blockIdx.x] = v[0];
+  if (arrive_last(&st->ticket[2], gridDim.x, &sflag)) {
+    double t[1];
+    reduce_partials<1>(k.partial, gridDim.x, t, sm);
+    if (threadIdx.x == 0) {
+      st->red_G[0] = t[0];
+      st->rz_cur = 1.0;
+      st->iter = 0;
+      st->done = 0;
+      st->status = 0;
+      __hip_atomic_store(&st->ticket[2], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
 // Error against the analytic solution u = F(1 - cx x² - cy y²)/(2cx + 2cy).
 __global__ __launch_bounds__(TJ) void kError(KParams k) {
   __shared__ double sm[8];
@@ -494,7 +555,11 @@ __global__ __launch_bounds__(TJ) void kError(KParams k) {
 // into st->res = {Σρ², Σr², Σ(ρ − r)², ΣB²}, block partials summed
 // in block order (deterministic).  store: ρ → the r-plane of x[bw] (the
 // three-step restart's r⁰; this kernel reads no r there).
-__global__ __launch_bounds__(TJ) void kResid(KParams k, int bw, int with_r, int store) {
+// Bp: the user right-hand side's dense nx × ny plane (FIELD; masked by the
+// ellipse like F), so the check — and the three-step restart's stored ρ —
+// belong to the user's problem.
+template <bool FIELD>
+__device__ __forceinline__ void resid_body(const KParams& k, int bw, int with_r, int store, const double* Bp) {
   __shared__ double sm[16];
   __shared__ int sflag;
   DevState* st = k.st;
@@ -507,7 +572,7 @@ __global__ __launch_bounds__(TJ) void kResid(KParams k, int bw, int with_r, int 
     const double x = k.A1 + (k.gi0 + li) * k.h1, y = k.A2 + (k.gj0 + lj) * k.h2;
     const CS c = cset_mem<false>(k, li, lj);
     const int64_t at = li * k.pitch + lj;
-    const double B = in_ellipse(x, y, k.cx, k.cy) ? k.F : 0.0;
+    const double B = in_ellipse(x, y, k.cx, k.cy) ? (FIELD ? Bp[idx] : k.F) : 0.0;
     const double rho = B - stencil<false>(k, c, wv[at - k.pitch], wv[at], wv[at + k.pitch], wv[at - 1], wv[at + 1]);
     a[0] += rho * rho;
     a[3] += B * B;
@@ -531,6 +596,13 @@ __global__ __launch_bounds__(TJ) void kResid(KParams k, int bw, int with_r, int 
       __hip_atomic_store(&st->ticket[3], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
+}
+__global__ __launch_bounds__(TJ) void kResid(KParams k, int bw, int with_r, int store) {
+  resid_body<false>(k, bw, with_r, store, nullptr);
+}
+__global__ __launch_bounds__(TJ) void kResidField(KParams k, int bw, int with_r, int store,
+                                                  const double* __restrict__ Bp) {
+  resid_body<true>(k, bw, with_r, store, Bp);
 }
 
 // w (owned nodes) → the p-plane of x[b] (kResid's operand).
@@ -651,6 +723,14 @@ void launch_init(const KParams& k, int init_random, unsigned long long seed, dou
   else hipLaunchKernelGGL(kInit<false>, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, init_random, seed, amp);
 }
 
+void launch_init_field(const KParams& k, const double* rhs, const double* w0, int init_random,
+                       unsigned long long seed, double amp, int variant, hipStream_t s) {
+  if (variant == 1)
+    hipLaunchKernelGGL(kInitField<true>, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, rhs, w0, init_random, seed, amp);
+  else
+    hipLaunchKernelGGL(kInitField<false>, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, rhs, w0, init_random, seed, amp);
+}
+
 void launch_F(const KParams& k, int par, int variant, hipStream_t s) {
   if (variant == 1) hipLaunchKernelGGL(kF<true>, dim3(k.nblocks), dim3(TJ), 0, s, k, par);
   else hipLaunchKernelGGL(kF<false>, dim3(k.nblocks), dim3(TJ), 0, s, k, par);
@@ -684,8 +764,9 @@ void launch_error(const KParams& k, hipStream_t s) {
   hipLaunchKernelGGL(kError, dim3(flat_blocks(k)), dim3(TJ), 0, s, k);
 }
 
-void launch_resid(const KParams& k, int bw, bool with_r, bool store, hipStream_t s) {
-  hipLaunchKernelGGL(kResid, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, bw, with_r ? 1 : 0, store ? 1 : 0);
+void launch_resid(const KParams& k, int bw, bool with_r, bool store, hipStream_t s, const double* rhs) {
+  if (rhs) hipLaunchKernelGGL(kResidField, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, bw, with_r ? 1 : 0, store ? 1 : 0, rhs);
+  else hipLaunchKernelGGL(kResid, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, bw, with_r ? 1 : 0, store ? 1 : 0);
 }
 void launch_w_to_p(const KParams& k, int b, hipStream_t s) {
   hipLaunchKernelGGL(kWtoP, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, b);

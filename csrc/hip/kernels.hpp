@@ -294,12 +294,17 @@ int resident_max_blocks_per_cu(size_t lds_bytes);
 
 void launch_init(const KParams& k, int init_random, unsigned long long seed, double amp, int variant,
                  hipStream_t s);
+// Init from user fields (device planes; either may be null): rhs dense nx × ny,
+// w0 dense (nx+2) × (ny+2) with its ring; w0 overrides init_random.
+void launch_init_field(const KParams& k, const double* rhs, const double* w0, int init_random,
+                       unsigned long long seed, double amp, int variant, hipStream_t s);
 void launch_F(const KParams& k, int par, int variant, hipStream_t s);
 void launch_G(const KParams& k, int par, int variant, hipStream_t s);
 void launch_error(const KParams& k, hipStream_t s);
 // True residual ρ = B − A w (w from the p-plane of x[bw], halo exchanged; r
 // from x[st->wpar] when with_r) → st->res; store: ρ → x[bw]'s r-plane.
-void launch_resid(const KParams& k, int bw, bool with_r, bool store, hipStream_t s);
+// rhs: the user right-hand side's device plane (dense nx × ny; null: F).
+void launch_resid(const KParams& k, int bw, bool with_r, bool store, hipStream_t s, const double* rhs = nullptr);
 void launch_w_to_p(const KParams& k, int b, hipStream_t s);   // owned w → the p-plane of x[b]
 void launch_zero_p(const KParams& k, int b, hipStream_t s);   // the p-plane of x[b] ← 0 (halos included)
 void launch_restart3(const KParams& k, hipStream_t s);        // three-step restart state (kRestart3)

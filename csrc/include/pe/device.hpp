@@ -145,6 +145,19 @@ class DeviceSolver {
   // Initial guess of the next reset() / solve() (bench: the BASELINE
   // random-init solve on the same solver as the zero-init one).
   void set_init(Init init, uint64_t seed, double amp);
+  // User fields of the next reset() / solve() (pe/fields.hpp), as this
+  // block's slices in host memory: `owned` nx × ny (block_field ring 0) for
+  // the right-hand side, `ringed` (nx+2) × (ny+2) (ring 1) for the initial
+  // guess, which overrides set_init.  nullptr clears a field (back to F /
+  // Init).  Uploaded on the solver stream into planes the solver owns
+  // (allocated when first set, kept until cleared); drops cached graphs.  The
+  // constructor's tuning always runs on the built-in problem.  A resumed
+  // solve needs the same rhs again (B is an input, not checkpointed state)
+  // and ignores w0.
+  void set_rhs(const double* owned);
+  void set_w0(const double* ringed);
+  bool user_rhs() const { return rhs_dev_ != nullptr; }
+  bool user_w0() const { return w0_dev_ != nullptr; }
   // Tuning probe: re-lay out the work items for `ti` rows per item, re-reading
   // the PE_* layout knobs (same allocation, so configurations compare at one
   // memory placement).  Drops cached graphs.
@@ -269,6 +282,7 @@ class DeviceSolver {
  private:
   void build_tables(int64_t rows_hi, int64_t cols_hi);
   void upload(void* dst, const void* src, size_t bytes);  // set-up data via pinned staging + copy kernel
+  void set_plane(double** plane, const double* host, int64_t n);  // set_rhs / set_w0
   void set_fused_fields(double* x0, double* x1, double* w);
   // item lists at `ti` rows per item: static layout or dynamic per-XCD shards (+ halo/interior overlap)
   void apply_layout(int ti);
@@ -343,6 +357,8 @@ class DeviceSolver {
   std::vector<int> rowcls_host_;  // host copy of the row classes (item cost estimates)
   double* halo_ = nullptr;    // send_dn, send_up, recv_dn, recv_up (nx each; ×4 single-sweep)
   int64_t hsize_ = 0;
+  double* rhs_dev_ = nullptr;  // user right-hand side, dense nx × ny (null: F)
+  double* w0_dev_ = nullptr;   // user initial guess, dense (nx+2) × (ny+2) with its ring (null: opt_.init)
   double* partial_ = nullptr;
   double* hist_ = nullptr;
   unsigned long long* stamps_ = nullptr;
@@ -429,9 +445,11 @@ class DeviceSolver {
 // P virtual ranks on ONE device (LocalComm).  Every rank runs the
 // same kernels and the same halo plan as under RCCL; the transport is
 // device-to-device copies + a cross-stream reduction kernel.
+// `fields`: user right-hand side / initial guess as global interior arrays;
+// every block takes its slices through block_field (pe/fields.hpp).
 SolveResult device_solve_group(const Problem& prob, int ranks, DecompMode mode, const SolveOptions& opt,
-                               std::vector<double>* w_out = nullptr);
+                               std::vector<double>* w_out = nullptr, const UserFields& fields = UserFields());
 SolveResult device_solve_group(const Problem& prob, const ProcessGrid& pg, const SolveOptions& opt,
-                               std::vector<double>* w_out = nullptr);
+                               std::vector<double>* w_out = nullptr, const UserFields& fields = UserFields());
 
 }  // namespace pe

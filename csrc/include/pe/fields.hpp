@@ -1,0 +1,36 @@
+// User fields of a solve: the right-hand side and the initial guess as arrays
+// over the global interior, and the one function that cuts a block's share
+// out of such an array (every backend and the Python binding slice with it).
+//
+// A global interior array is (M-1) × (N-1), row-major in i, entry
+// [i-1][j-1] at node (x_i, y_j) — the shape `w_out` / `--dump` produce.
+//   rhs: B_ij = rhs_ij at nodes inside the ellipse, 0 elsewhere (the
+//        reference's mask, stage2-mpi/poisson_mpi_decomp.cpp:160-169, with
+//        F_VAL replaced per node);
+//   w0:  the initial guess, r⁰ = B − A w⁰ (box-boundary values are 0; nodes
+//        outside the ellipse are unknowns of the fictitious-domain system and
+//        may start non-zero).  Overrides SolveOptions::init.
+// A null field keeps the built-in path (constant F / Init) bit for bit.
+#pragma once
+
+#include <cstdint>
+#include <vector>
+
+#include "pe/decomp.hpp"
+
+namespace pe {
+
+struct UserFields {
+  const double* rhs = nullptr;
+  const double* w0 = nullptr;
+};
+
+// Block `blk`'s share of the global interior array `g` of an M × N grid,
+// dense row-major.  ring = 0: the owned nx × ny part (element [li-1][lj-1] =
+// local node (li, lj)); ring = 1: the owned part plus a one-node ring,
+// (nx+2) × (ny+2) (element [li][lj]), the ring holding the neighbours' values
+// and zeros on the box boundary.  Local (li, lj) is global (i0-1+li, j0-1+lj)
+// as in Block; all indices 64-bit.
+std::vector<double> block_field(const double* g, int M, int N, const Block& blk, int ring);
+
+}  // namespace pe

@@ -13,6 +13,7 @@
 
 #include "pe/comm.hpp"
 #include "pe/decomp.hpp"
+#include "pe/fields.hpp"
 #include "pe/problem.hpp"
 
 namespace pe {
@@ -117,16 +118,21 @@ struct SolveResult {
 // Reference-faithful PCG on one block of the decomposition; `comm` supplies
 // halo exchange + reductions (SelfHostComm for serial/OpenMP runs).  When
 // `w_out` is non-null the owned block of w is copied out row-major (nx × ny).
+// `fields`: the user right-hand side / initial guess as GLOBAL interior arrays
+// (pe/fields.hpp; every rank passes the same arrays and takes its slice).  With
+// a user rhs the analytic solution does not apply: l2_err = max_err = -1.
 SolveResult cpu_pcg(const Problem& prob, const Block& blk, HostComm& comm,
-                    const SolveOptions& opt, std::vector<double>* w_out = nullptr);
+                    const SolveOptions& opt, std::vector<double>* w_out = nullptr,
+                    const UserFields& fields = UserFields());
 
 // Run P thread-ranks (ThreadHostComm) × `opt.threads` OpenMP threads each and
 // return rank 0's result; `w_out` receives the gathered global interior
 // ((M-1) × (N-1), row-major in i) when non-null.
 SolveResult cpu_pcg_threads(const Problem& prob, int ranks, DecompMode mode,
-                            const SolveOptions& opt, std::vector<double>* w_out = nullptr);
+                            const SolveOptions& opt, std::vector<double>* w_out = nullptr,
+                            const UserFields& fields = UserFields());
 SolveResult cpu_pcg_threads(const Problem& prob, const ProcessGrid& pg, const SolveOptions& opt,
-                            std::vector<double>* w_out = nullptr);
+                            std::vector<double>* w_out = nullptr, const UserFields& fields = UserFields());
 
 // Legacy-format report lines (reference stdout formats, §2.9 of SURVEY).
 std::string format_result_legacy(const Problem& prob, const SolveResult& r, int nranks,

@@ -10,6 +10,17 @@
 Prints the reference's result lines (``--legacy``, default) and/or a JSON
 report (``--json``), the L2/max error against the analytic solution, and
 optionally dumps w (``--dump w.npy``, plus ``--pgm w.pgm``).
+
+``--rhs FILE.npy`` / ``--w0 FILE.npy`` solve for a user right-hand side from
+a user initial guess: float64 arrays of the global interior, shape
+(M-1, N-1), entry [i-1, j-1] at node (x_i, y_j) — what ``--dump`` writes, so
+the dump of one run is a valid ``--w0`` of the next:
+
+    python -m poisson_ellipse_openmp_mpi_cuda_amd.cli --rhs f.npy --dump w.npy 400 600
+    python -m poisson_ellipse_openmp_mpi_cuda_amd.cli --rhs f.npy --w0 w.npy 400 600
+
+Checkpoints hold the iteration state, not the right-hand side: ``--resume``
+needs the same ``--rhs`` again, and ignores ``--w0``.
 """
 
 from __future__ import annotations
@@ -18,8 +29,10 @@ import argparse
 import os
 import sys
 
+import numpy as np
+
 from .models.ellipse import PRESETS, EllipseProblem
-from .solver import BACKENDS, solve
+from .solver import BACKENDS, solve, user_field
 from .utils import dump as _dump
 from .utils.report import json_report, legacy_lines
 
@@ -37,6 +50,13 @@ def build_parser():
                          "default: device for the GPU backends, aspect otherwise")
     ap.add_argument("--init", choices=("zero", "random"), default="zero")
     ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--rhs", default=None, metavar="FILE.npy",
+                    help="user right-hand side: float64 (M-1, N-1) array of the interior (masked by the ellipse; "
+                         "the L2 / max error against the analytic solution is then not reported); a resumed solve "
+                         "(--resume) needs the same --rhs again: checkpoints do not hold it")
+    ap.add_argument("--w0", default=None, metavar="FILE.npy",
+                    help="user initial guess: float64 (M-1, N-1) array, e.g. the --dump of an earlier run; "
+                         "overrides --init; ignored with --resume")
     ap.add_argument("--tol", type=float, default=1e-6)
     ap.add_argument("--max-iter", type=int, default=-1)
     ap.add_argument("--norm", choices=("weighted", "unweighted"), default="weighted")
@@ -67,16 +87,25 @@ def main(argv=None) -> int:
     prob.max_iter = a.max_iter
     prob.norm = a.norm
     want_w = bool(a.dump or a.pgm)
+    try:
+        rhs = None if a.rhs is None else user_field("--rhs", np.load(a.rhs, allow_pickle=False), prob)
+        w0 = None if a.w0 is None else user_field("--w0", np.load(a.w0, allow_pickle=False), prob)
+    except (OSError, ValueError) as e:
+        print(f"error: {e}", file=sys.stderr)
+        return 2
     rep = solve(prob, backend=a.backend, ranks=a.ranks, threads=a.threads, decomp=a.decomp, init=a.init,
                 seed=a.seed, return_w=want_w, variant=a.variant, timing=a.timing, graph=a.graph and not a.no_graph,
                 algo=a.algo, checkpoint=a.checkpoint, checkpoint_every=a.checkpoint_every, resume=a.resume,
-                log_every=a.log_every)
+                log_every=a.log_every, rhs=rhs, w0=w0)
     if rep.rank != 0:
         return 0
     if not a.quiet:
         print(legacy_lines(rep, a.tol))
-        print(f"   Process grid {rep.Px}x{rep.Py} | iters/s ~ {rep.iters_per_s:.1f} | L2 error in D ~ {rep.l2_err:.6e}"
-              f" | max error in D ~ {rep.max_err:.6e}")
+        if rhs is None:
+            err = f"L2 error in D ~ {rep.l2_err:.6e} | max error in D ~ {rep.max_err:.6e}"
+        else:
+            err = "L2 error in D ~ n/a (user right-hand side)"
+        print(f"   Process grid {rep.Px}x{rep.Py} | iters/s ~ {rep.iters_per_s:.1f} | {err}")
     if a.json:
         print(json_report(rep))
     if want_w and rep.w is not None:

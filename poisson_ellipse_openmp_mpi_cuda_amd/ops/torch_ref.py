@@ -9,6 +9,14 @@ runs on any torch device ("cpu" here, "cuda" = HIP on the GPU box).
 Arrays use the reference's global indexing: shape (M+1, N+1), index [i, j]
 for node (x_i, y_j); interior unknowns are [1:M, 1:N]; the box boundary is
 held at 0 (Dirichlet).
+
+User fields (keyword-only ``rhs``, ``w0`` of assemble / pcg / single_sweep /
+two_step / three_step) are INTERIOR arrays of shape (M-1, N-1), numpy or
+torch, entry [i-1, j-1] at node (x_i, y_j) — the shape every backend takes
+and ``return_w`` / ``--dump`` produce.  ``rhs`` is masked by the ellipse
+(B = rhs inside, 0 outside), ``w0`` starts the recurrence at r⁰ = B − A w⁰.
+None keeps the built-in constant F / zero start bit for bit.  (pcg's older
+positional ``w0`` also still accepts a full (M+1, N+1) tensor.)
 """
 
 from __future__ import annotations
@@ -46,8 +54,25 @@ def _face_coef_np(l, h, eps):
     return np.where(np.abs(l - h) < 1e-9, 1.0, out)
 
 
-def assemble(prob: EllipseProblem, device="cpu"):
-    """Coefficients a, b (shape (M+1, N+1); row/col 0 unused) and RHS B.
+def embed(prob: EllipseProblem, f, device="cpu") -> torch.Tensor:
+    """An interior array (M-1, N-1) as an fp64 (M+1, N+1) tensor with a zero
+    box boundary (a full (M+1, N+1) tensor passes through)."""
+    import numpy as np
+
+    t = f.detach().to("cpu", torch.float64) if isinstance(f, torch.Tensor) else torch.from_numpy(
+        np.array(f, dtype=np.float64, order="C"))
+    if tuple(t.shape) == (prob.M + 1, prob.N + 1):
+        return t.clone().to(device)
+    if tuple(t.shape) != (prob.M - 1, prob.N - 1):
+        raise ValueError(f"field: expected shape {(prob.M - 1, prob.N - 1)}, got {tuple(t.shape)}")
+    out = torch.zeros(prob.M + 1, prob.N + 1, dtype=torch.float64)
+    out[1:-1, 1:-1] = t
+    return out.to(device)
+
+
+def assemble(prob: EllipseProblem, device="cpu", *, rhs=None):
+    """Coefficients a, b (shape (M+1, N+1); row/col 0 unused) and RHS B
+    (rhs: a user right-hand side over the interior, masked by the ellipse).
 
     Built with numpy (hardware IEEE sqrt / division: bit-identical to the
     reference's C++ fic_reg) and moved to `device`; PyTorch's CPU sqrt and
@@ -75,7 +100,7 @@ def assemble(prob: EllipseProblem, device="cpu"):
     a = _face_coef_np(la, h2, eps)
     b = _face_coef_np(lb, h1, eps)
     inside = (prob.cx * X * X + prob.cy * Y * Y) < 1.0
-    B = np.where(inside, prob.F, 0.0)
+    B = np.where(inside, prob.F if rhs is None else embed(prob, rhs).numpy(), 0.0)
     B[0, :] = B[-1, :] = 0.0
     B[:, 0] = B[:, -1] = 0.0
     t = lambda v: torch.from_numpy(np.ascontiguousarray(v)).to(device)  # noqa: E731
@@ -120,13 +145,23 @@ class TorchPCGResult:
     history: list
 
 
-def pcg(prob: EllipseProblem, device="cpu", w0: Optional[torch.Tensor] = None, max_iter: Optional[int] = None,
-        keep_history: bool = False) -> TorchPCGResult:
-    """Reference-algorithm Jacobi PCG (stage2 solve_mpi order of operations)."""
-    a, b, B = assemble(prob, device)
+def _start(prob, device, rhs, w0):
+    """a, b, B and the start (r⁰, w⁰) of the sweep recurrences."""
+    a, b, B = assemble(prob, device, rhs=rhs)
+    if w0 is None:
+        return a, b, B, B.clone(), torch.zeros_like(B)
+    w = embed(prob, w0, device)
+    return a, b, B, B - apply_A(w, a, b, prob.h1, prob.h2), w
+
+
+def pcg(prob: EllipseProblem, device="cpu", w0=None, max_iter: Optional[int] = None,
+        keep_history: bool = False, *, rhs=None) -> TorchPCGResult:
+    """Reference-algorithm Jacobi PCG (stage2 solve_mpi order of operations).
+    With a user rhs the analytic solution does not apply: l2_err = max_err = -1."""
+    a, b, B = assemble(prob, device, rhs=rhs)
     h1, h2 = prob.h1, prob.h2
     D = diag(a, b, h1, h2)
-    w = torch.zeros_like(B) if w0 is None else w0.clone()
+    w = torch.zeros_like(B) if w0 is None else embed(prob, w0, device)
     r = B - apply_A(w, a, b, h1, h2)
     r[0, :] = r[-1, :] = 0
     r[:, 0] = r[:, -1] = 0
@@ -158,7 +193,7 @@ def pcg(prob: EllipseProblem, device="cpu", w0: Optional[torch.Tensor] = None, m
         beta = zr_new / zr_old
         zr_old = zr_new
         p = z + beta * p
-    l2, mx = error_vs_analytic(prob, w)
+    l2, mx = error_vs_analytic(prob, w) if rhs is None else (-1.0, -1.0)
     return TorchPCGResult(k, converged, w, l2, mx, hist)
 
 
@@ -173,7 +208,7 @@ class SingleSweepState:
     w: torch.Tensor
 
 
-def single_sweep(prob: EllipseProblem, iters: int, device="cpu") -> SingleSweepState:
+def single_sweep(prob: EllipseProblem, iters: int, device="cpu", *, rhs=None, w0=None) -> SingleSweepState:
     """The single-reduction recurrence of the device sweep kernels
     (csrc/hip/fused.hip header, sweep_scalars), on the reference operator.
 
@@ -182,14 +217,12 @@ def single_sweep(prob: EllipseProblem, iters: int, device="cpu") -> SingleSweepS
         g = R₀h², β = g/g_prev (0 at k = 1), den = (R₁ + 2βR₂ + β²R₃)h², α = g/den
         p = z + βp, s = Ap, w += αp, r -= αs, z = D⁻¹r, q = Az → sums of sweep k.
     Algebraically the reference PCG (stage2-mpi/poisson_mpi_decomp.cpp:400-457)."""
-    a, b, B = assemble(prob, device)
+    a, b, B, r, w = _start(prob, device, rhs, w0)
     h1, h2 = prob.h1, prob.h2
     hh = h1 * h2
     D = diag(a, b, h1, h2)
     inner = lambda u, v: float((u[1:-1, 1:-1] * v[1:-1, 1:-1]).sum())  # noqa: E731  (unweighted)
-    r = B.clone()
     p = torch.zeros_like(B)
-    w = torch.zeros_like(B)
     s = torch.zeros_like(B)
     z = apply_Dinv(r, D)
     q = apply_A(z, a, b, h1, h2)
@@ -265,13 +298,13 @@ def two_step_scalars(R, gprev: float, K: int, hh: float, weighted: bool = True):
     return g1, b1, a1, d1, g2, b2, a2, d2, den1, den2
 
 
-def two_step(prob: EllipseProblem, sweeps: int, device="cpu") -> TwoStepState:
+def two_step(prob: EllipseProblem, sweeps: int, device="cpu", *, rhs=None, w0=None) -> TwoStepState:
     """The two-iterations-per-sweep recurrence of csrc/hip/fused2.hip on the
     reference operator (divisions): S_0 (the sums around r₀ = B, p₀ = 0),
     then `sweeps` sweeps, each advancing iterations K+1 and K+2 with scalars
     from the previous sweep's 20 sums.  Algebraically the reference PCG
     (stage2-mpi/poisson_mpi_decomp.cpp:400-457), two iterations at a time."""
-    a, b, B = assemble(prob, device)
+    a, b, B, r, w = _start(prob, device, rhs, w0)
     h1, h2 = prob.h1, prob.h2
     hh = h1 * h2
     D = diag(a, b, h1, h2)
@@ -279,9 +312,7 @@ def two_step(prob: EllipseProblem, sweeps: int, device="cpu") -> TwoStepState:
     m = D != 0
     Dinv[m] = 1.0 / D[m]
     A = lambda u: apply_A(u, a, b, h1, h2)  # noqa: E731
-    r = B.clone()
     p = torch.zeros_like(B)
-    w = torch.zeros_like(B)
     sums = [two_step_sums(r, p, a, b, h1, h2, Dinv)]
     alphas, betas, diffs = [], [], []
     gprev = 0.0
@@ -370,13 +401,13 @@ def three_step_scalars(R, gprev: float, K: int, hh: float, lim: int = 3):
     return out
 
 
-def three_step(prob: EllipseProblem, sweeps: int, device="cpu") -> ThreeStepState:
+def three_step(prob: EllipseProblem, sweeps: int, device="cpu", *, rhs=None, w0=None) -> ThreeStepState:
     """The three-iterations-per-sweep recurrence of csrc/hip/fused3.hip on the
     reference operator (divisions): S_0, then `sweeps` full sweeps, each
     advancing iterations K+1..K+3 with scalars from the previous sweep's 16
     moments; the sweep's own ‖p_i‖² give the (late) ‖Δw‖.  Algebraically the
     reference PCG (stage2-mpi/poisson_mpi_decomp.cpp:400-457)."""
-    a, b, B = assemble(prob, device)
+    a, b, B, r, w = _start(prob, device, rhs, w0)
     h1, h2 = prob.h1, prob.h2
     hh = h1 * h2
     D = diag(a, b, h1, h2)
@@ -386,9 +417,7 @@ def three_step(prob: EllipseProblem, sweeps: int, device="cpu") -> ThreeStepStat
     A = lambda u: apply_A(u, a, b, h1, h2)  # noqa: E731
     inner = lambda u, v: float((u[1:-1, 1:-1] * v[1:-1, 1:-1]).sum())  # noqa: E731
     weighted = prob.norm == "weighted"
-    r = B.clone()
     p = torch.zeros_like(B)
-    w = torch.zeros_like(B)
     sums = [three_step_moments(r, p, a, b, h1, h2, Dinv) + [0.0, 0.0, 0.0]]
     alphas, betas, diffs = [], [], []
     gprev = 0.0

@@ -118,6 +118,28 @@ def _options(init="zero", seed=1234, threads=1, chunk=0, graph=False, timing=Fal
     return o
 
 
+def user_field(name: str, f, prob: EllipseProblem) -> Optional[np.ndarray]:
+    """A user field (rhs / w0) as a C-contiguous float64 array of the global
+    interior, shape (M-1, N-1), entry [i-1, j-1] at node (x_i, y_j) — or
+    ValueError: wrong shape, data that float64 cannot hold without loss
+    (wider floats, large integers, complex, non-numeric), non-finite values."""
+    if f is None:
+        return None
+    if hasattr(f, "detach") and hasattr(f, "numpy"):  # a CPU torch tensor
+        f = f.detach().numpy()
+    a = np.asarray(f)
+    if a.dtype.kind not in "biuf":
+        raise ValueError(f"{name}: dtype {a.dtype} is not real numeric data")
+    if a.shape != (prob.M - 1, prob.N - 1):
+        raise ValueError(f"{name}: expected the global interior, shape {(prob.M - 1, prob.N - 1)}, got {a.shape}")
+    out = np.ascontiguousarray(a, dtype=np.float64)
+    if a.dtype != np.float64 and not np.array_equal(out.astype(a.dtype), a):
+        raise ValueError(f"{name}: {a.dtype} values cannot be converted to float64 without loss")
+    if not np.isfinite(out).all():
+        raise ValueError(f"{name}: non-finite values")
+    return out
+
+
 def _report(backend, prob, res, ranks, threads, init, w=None, rank=0) -> SolveReport:
     return SolveReport(
         backend=backend, M=prob.M, N=prob.N, ranks=ranks, Px=res.Px, Py=res.Py, threads=threads,
@@ -133,8 +155,20 @@ def _report(backend, prob, res, ranks, threads, init, w=None, rank=0) -> SolveRe
 
 
 def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: int = 1, decomp: str | None = None,
-          init: str = "zero", seed: int = 1234, return_w: bool = False, device: str = "cuda", **kw) -> SolveReport:
+          init: str = "zero", seed: int = 1234, return_w: bool = False, device: str = "cuda", rhs=None, w0=None,
+          **kw) -> SolveReport:
     """Solve the fictitious-domain Poisson problem with the chosen backend.
+
+    ``rhs`` / ``w0`` (every backend): a user right-hand side and initial guess
+    as float64 arrays of the global interior, shape (M-1, N-1), entry
+    [i-1, j-1] at node (x_i, y_j) — the shape ``return_w`` returns, so a
+    returned ``w`` is a valid ``w0``.  B = rhs inside the ellipse and 0
+    outside; r⁰ = B − A w⁰; ``w0`` overrides ``init`` (the report's ``init``
+    is then "field").  With ``rhs`` the analytic solution does not apply and
+    ``l2_err`` / ``max_err`` are −1.  On multi-rank runs every rank passes the
+    same global arrays and takes its slice.  A resumed solve (``resume=``)
+    needs the same ``rhs`` again and ignores ``w0``.  None keeps the built-in
+    constant F / ``init`` path bit for bit.
 
     For ``hip`` with torch.distributed initialised and world > 1 this is the
     per-rank call of a multi-GPU job (every rank calls it; rank 0's report
@@ -142,6 +176,10 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
     """
     if backend not in BACKENDS:
         raise ValueError(f"backend must be one of {BACKENDS}")
+    rhs = user_field("rhs", rhs, prob)
+    w0 = user_field("w0", w0, prob)
+    if w0 is not None:
+        init = "field"
     decomp = decomp or _decomp.default_spec(backend)
     nat = native()
     P = prob.to_native()
@@ -150,7 +188,7 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
         nranks = ranks if backend == "ranks" else 1
         opt = _options(init, seed, t, keep_history=kw.get("keep_history", False), log_every=kw.get("log_every", 0))
         res, w = nat.cpu_solve_grid(P, _decomp.grid(nranks, prob.M, prob.N, decomp if backend == "ranks" else "reference"),
-                                    opt, return_w)
+                                    opt, return_w, rhs, w0)
         return _report(backend, prob, res, nranks, t, init, None if w is None else np.asarray(w))
     if backend == "torch":
         import torch
@@ -160,17 +198,18 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
         if device.startswith("cuda") and not torch.cuda.is_available():
             device = "cpu"
         t0 = time.perf_counter()
-        r = torch_ref.pcg(prob, device=device, keep_history=kw.get("keep_history", False))
+        r = torch_ref.pcg(prob, device=device, w0=w0, keep_history=kw.get("keep_history", False), rhs=rhs)
         dt = time.perf_counter() - t0
         timers = dict(solver=dt, iterate=dt)
         return SolveReport("torch", prob.M, prob.N, 1, 1, 1, 1, r.iters, r.converged, False,
-                           r.history[-1] if r.history else 0.0, timers, r.l2_err, r.max_err, -1.0, "zero",
+                           r.history[-1] if r.history else 0.0, timers, r.l2_err, r.max_err, -1.0,
+                           "zero" if w0 is None else "field",
                            r.w[1:-1, 1:-1].cpu().numpy() if return_w else None)
     if backend == "hip-group":
         opt = _options(init, seed, chunk=kw.get("chunk", 0), timing=kw.get("timing", False),
                        variant=kw.get("variant", 0), check_tol=kw.get("check_tol", True),
                        algo=kw.get("algo", "auto"))
-        res, w = nat.device_solve_group_grid(P, _decomp.grid(ranks, prob.M, prob.N, decomp), opt, return_w)
+        res, w = nat.device_solve_group_grid(P, _decomp.grid(ranks, prob.M, prob.N, decomp), opt, return_w, rhs, w0)
         return _report(backend, prob, res, ranks, 1, init, None if w is None else np.asarray(w))
     # distributed backends
     from .parallel import dist as _dist
@@ -179,7 +218,7 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
         ctx = _dist.init()
         blk = _decomp.block(prob.M, prob.N, ctx.world, ctx.rank, decomp)
         opt = _options(init, seed, max(1, threads))
-        res, w = nat.cpu_solve_rank(P, blk, *_dist.gloo_callbacks(), opt, True)
+        res, w = nat.cpu_solve_rank(P, blk, *_dist.gloo_callbacks(), opt, True, rhs, w0)
         wg = _dist.gather_blocks(ctx, prob, blk, np.asarray(w)) if return_w else None
         return _report(backend, prob, res, ctx.world, threads, init, wg, ctx.rank)
     # hip
@@ -207,6 +246,10 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
         blk = _decomp.block(prob.M, prob.N, world, rank, decomp)
     solver = nat.DeviceSolver(P, blk, comm, opt)
     try:
+        if rhs is not None or w0 is not None:  # this rank's slices of the global arrays
+            rhs_l, w0_l = nat.block_fields(prob.M, prob.N, blk, rhs, w0)
+            solver.set_rhs(rhs_l)
+            solver.set_w0(w0_l)
         res = solver.solve()
     except Exception:
         if comm is not None:
