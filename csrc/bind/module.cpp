@@ -541,6 +541,38 @@ PYBIND11_MODULE(_native, m) {
           },
           py::arg("ringed"),
           "this block's (nx+2) × (ny+2) slice of the initial guess with its ring (block_fields), or None for init")
+      .def(
+          "set_rhs_device",
+          [](DeviceSolver& s, uintptr_t ptr, int64_t si, int64_t sj, bool f32, uintptr_t stream) {
+            s.set_rhs_device(reinterpret_cast<const void*>(ptr), si, sj, f32, reinterpret_cast<hipStream_t>(stream));
+          },
+          py::arg("ptr"), py::arg("stride_i"), py::arg("stride_j"), py::arg("f32") = false, py::arg("stream") = 0,
+          "the right-hand side as the GLOBAL (M-1) × (N-1) array in device memory: address of element [0][0], "
+          "element strides, float32 flag, the producing stream's handle (0 clears the field when ptr is 0)")
+      .def(
+          "set_w0_device",
+          [](DeviceSolver& s, uintptr_t ptr, int64_t si, int64_t sj, bool f32, uintptr_t stream) {
+            s.set_w0_device(reinterpret_cast<const void*>(ptr), si, sj, f32, reinterpret_cast<hipStream_t>(stream));
+          },
+          py::arg("ptr"), py::arg("stride_i"), py::arg("stride_j"), py::arg("f32") = false, py::arg("stream") = 0,
+          "the initial guess as the GLOBAL (M-1) × (N-1) array in device memory (see set_rhs_device)")
+      .def(
+          "copy_w_device",
+          [](DeviceSolver& s, uintptr_t ptr, int64_t si, int64_t sj, int64_t off_i, int64_t off_j, uintptr_t stream) {
+            s.copy_w_device(reinterpret_cast<double*>(ptr), si, sj, off_i, off_j, reinterpret_cast<hipStream_t>(stream));
+          },
+          py::arg("ptr"), py::arg("stride_i"), py::arg("stride_j"), py::arg("off_i") = 0, py::arg("off_j") = 0,
+          py::arg("stream") = 0,
+          "the owned w into float64 device memory at element offset (off_i, off_j) of `ptr`, ordered with `stream`")
+      .def(
+          "user_plane",
+          [](DeviceSolver& s, int which) -> py::object {
+            std::vector<double> v = s.user_plane(which);
+            if (v.empty()) return py::none();
+            const int64_t ring = which ? 1 : 0;
+            return to_array(std::move(v), s.block().nx + 2 * ring, s.block().ny + 2 * ring);
+          },
+          py::arg("which"), "host copy of the user plane the solve reads (0 rhs, 1 w0), None when unset")
       .def_property_readonly("user_rhs", &DeviceSolver::user_rhs)
       .def_property_readonly("user_w0", &DeviceSolver::user_w0)
       .def("relayout", &DeviceSolver::relayout, py::arg("ti"), py::arg("order") = -1)
@@ -706,6 +738,56 @@ PYBIND11_MODULE(_native, m) {
       },
       py::arg("prob"), py::arg("grid"), py::arg("opt") = SolveOptions(), py::arg("return_w") = false,
       py::arg("rhs") = py::none(), py::arg("w0") = py::none());
+
+  // The same with fields and / or the result in device memory: rhs_dev /
+  // w0_dev = (address of element [0][0], stride_i, stride_j, float32 flag) of
+  // the global interior array or None, w_dev = (address, stride_i, stride_j)
+  // of a float64 (M-1) × (N-1) destination or None, `stream` the caller's
+  // stream handle.  Host fields may be mixed in (a field given both ways is
+  // taken from the device).
+  m.def(
+      "device_solve_group_grid_device",
+      [](const Problem& P, const ProcessGrid& pg, const SolveOptions& opt, bool return_w, py::object rhs,
+         py::object w0, py::object rhs_dev, py::object w0_dev, py::object w_dev, uintptr_t stream) {
+        FieldArr hr, hw;
+        UserFields uf;
+        uf.rhs = field_ptr(rhs, P.M - 1, P.N - 1, "rhs", hr);
+        uf.w0 = field_ptr(w0, P.M - 1, P.N - 1, "w0", hw);
+        DeviceFields df;
+        df.stream = reinterpret_cast<hipStream_t>(stream);
+        if (!rhs_dev.is_none()) {
+          auto t = rhs_dev.cast<std::tuple<uintptr_t, int64_t, int64_t, bool>>();
+          df.rhs = reinterpret_cast<const void*>(std::get<0>(t));
+          df.rhs_si = std::get<1>(t);
+          df.rhs_sj = std::get<2>(t);
+          df.rhs_f32 = std::get<3>(t);
+        }
+        if (!w0_dev.is_none()) {
+          auto t = w0_dev.cast<std::tuple<uintptr_t, int64_t, int64_t, bool>>();
+          df.w0 = reinterpret_cast<const void*>(std::get<0>(t));
+          df.w0_si = std::get<1>(t);
+          df.w0_sj = std::get<2>(t);
+          df.w0_f32 = std::get<3>(t);
+        }
+        if (!w_dev.is_none()) {
+          auto t = w_dev.cast<std::tuple<uintptr_t, int64_t, int64_t>>();
+          df.w_dst = reinterpret_cast<double*>(std::get<0>(t));
+          df.w_si = std::get<1>(t);
+          df.w_sj = std::get<2>(t);
+        }
+        std::vector<double> w;
+        SolveResult r;
+        {
+          py::gil_scoped_release nogil;
+          r = device_solve_group(P, pg, opt, return_w ? &w : nullptr, uf, df);
+        }
+        py::object wa = py::none();
+        if (return_w) wa = to_array(std::move(w), P.M - 1, P.N - 1);
+        return py::make_tuple(r, wa);
+      },
+      py::arg("prob"), py::arg("grid"), py::arg("opt") = SolveOptions(), py::arg("return_w") = false,
+      py::arg("rhs") = py::none(), py::arg("w0") = py::none(), py::arg("rhs_dev") = py::none(),
+      py::arg("w0_dev") = py::none(), py::arg("w_dev") = py::none(), py::arg("stream") = 0);
 
   // Single-shot device ops for numerics tests: `p` is a full local field
   // (rows × pitch, halo included); returns arrays of the same shape.

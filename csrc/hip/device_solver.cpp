@@ -137,6 +137,7 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
 
   mark("start");
   stream_ = acquire_stream();  // (pooled: set_device created one — runtime.cpp)
+  device_ = current_device();
   mark("stream");
   // Peer access of this rank's device toward every rank's (first cross-device
   // run diagnostics: the halo push and the in-sweep sums map peers' memory):
@@ -575,6 +576,84 @@ void DeviceSolver::set_rhs(const double* owned) { set_plane(&rhs_dev_, owned, bl
 
 void DeviceSolver::set_w0(const double* ringed) { set_plane(&w0_dev_, ringed, (blk_.nx + 2) * (blk_.ny + 2)); }
 
+// Device memory of this solver's device at elements [0] and [last] of `p`
+// (hipPointerGetAttributes), and — where the runtime knows the allocation's
+// range — both inside one allocation.  Throws before anything is launched.
+void DeviceSolver::check_device_span(const void* p, int64_t last, size_t elem, const char* what) const {
+  const std::string name(what);
+  if (last < 0) throw std::invalid_argument(name + ": negative extent");
+  const char* first = static_cast<const char*>(p);
+  const char* end = first + size_t(last) * elem;  // the last element
+  for (const char* q : {first, end}) {
+    hipPointerAttribute_t at;
+    std::memset(&at, 0, sizeof(at));
+    const hipError_t e = hipPointerGetAttributes(&at, q);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();  // (an unregistered host pointer: not a sticky error)
+      throw std::invalid_argument(name + ": not a device pointer (" + hipGetErrorString(e) + ")");
+    }
+    if (at.type != hipMemoryTypeDevice)
+      throw std::invalid_argument(name + ": not device memory (host, managed or unregistered pointer)");
+    if (at.device != device_)
+      throw std::invalid_argument(name + ": memory of device " + std::to_string(at.device) + ", the solver runs on device " +
+                                  std::to_string(device_));
+  }
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<char*>(first)) == hipSuccess) {
+    if (end + elem > static_cast<const char*>(base) + size)
+      throw std::invalid_argument(name + ": shape and strides reach past the end of the allocation");
+  } else {
+    (void)hipGetLastError();
+  }
+}
+
+void DeviceSolver::io_events() {
+  for (hipEvent_t& e : ev_io_)
+    if (!e) PE_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+}
+
+void DeviceSolver::set_plane_device(double** plane, int ring, const void* g, int64_t si, int64_t sj, bool f32,
+                                    hipStream_t producer, const char* what) {
+  if (!g) {
+    set_plane(plane, nullptr, 0);
+    return;
+  }
+  const int64_t gnx = int64_t(prob_.M) - 1, gny = int64_t(prob_.N) - 1;
+  if (si < 0 || sj < 0) throw std::invalid_argument(std::string(what) + ": negative stride");
+  check_device_span(g, (gnx - 1) * si + (gny - 1) * sj, f32 ? sizeof(float) : sizeof(double), what);
+  for (auto& gr : graphs_) PE_HIP_CHECK(hipGraphExecDestroy(gr.second));
+  graphs_.clear();
+  io_events();
+  const int64_t rows = blk_.nx + 2 * ring, cols = blk_.ny + 2 * ring;
+  if (!*plane) PE_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(plane), sizeof(double) * size_t(rows * cols)));
+  PE_HIP_CHECK(hipEventRecord(ev_io_[0], producer));
+  PE_HIP_CHECK(hipStreamWaitEvent(stream_, ev_io_[0], 0));
+  dev::launch_slice_field(g, f32, si, sj, gnx, gny, blk_.i0, blk_.j0, blk_.nx, blk_.ny, ring, *plane, stream_);
+  PE_HIP_CHECK(hipGetLastError());
+  PE_HIP_CHECK(hipEventRecord(ev_io_[1], stream_));
+  PE_HIP_CHECK(hipStreamWaitEvent(producer, ev_io_[1], 0));
+}
+
+void DeviceSolver::set_rhs_device(const void* g, int64_t si, int64_t sj, bool f32, hipStream_t producer) {
+  set_plane_device(&rhs_dev_, 0, g, si, sj, f32, producer, "rhs");
+}
+
+void DeviceSolver::set_w0_device(const void* g, int64_t si, int64_t sj, bool f32, hipStream_t producer) {
+  set_plane_device(&w0_dev_, 1, g, si, sj, f32, producer, "w0");
+}
+
+std::vector<double> DeviceSolver::user_plane(int which) {
+  if (which != 0 && which != 1) throw std::invalid_argument("user_plane: 0 (rhs) or 1 (w0)");
+  const double* plane = which ? w0_dev_ : rhs_dev_;
+  if (!plane) return {};
+  const int64_t ring = which;
+  std::vector<double> v(size_t((blk_.nx + 2 * ring) * (blk_.ny + 2 * ring)));
+  PE_HIP_CHECK(hipMemcpyAsync(v.data(), plane, sizeof(double) * v.size(), hipMemcpyDeviceToHost, stream_));
+  PE_HIP_CHECK(hipStreamSynchronize(stream_));
+  return v;
+}
+
 void DeviceSolver::set_fused_fields(double* x0, double* x1, double* w) {
   KParams& k = *kp_;
   fields_ = x0;
@@ -624,6 +703,8 @@ DeviceSolver::~DeviceSolver() {
   (void)hipEventDestroy(ev_[0]);
   (void)hipEventDestroy(ev_[1]);
   (void)hipEventDestroy(ev_sync_);
+  for (hipEvent_t e : ev_io_)
+    if (e) (void)hipEventDestroy(e);
   (void)hipEventDestroy(t0_);
   (void)hipEventDestroy(t1_);
   for (const PhaseRec& r : recs_) {
@@ -1420,6 +1501,22 @@ void DeviceSolver::copy_w(double* host, bool owned_only) {
   PE_HIP_CHECK(hipStreamSynchronize(stream_));
 }
 
+void DeviceSolver::copy_w_device(double* dst, int64_t si, int64_t sj, int64_t off_i, int64_t off_j,
+                                 hipStream_t consumer) {
+  if (!dst) throw std::invalid_argument("w: null destination");
+  if (si < 0 || sj < 0 || off_i < 0 || off_j < 0) throw std::invalid_argument("w: negative stride or offset");
+  // (the check spans the destination from its element [0][0] to this block's last element)
+  check_device_span(dst, (off_i + blk_.nx - 1) * si + (off_j + blk_.ny - 1) * sj, sizeof(double), "w");
+  io_events();
+  PE_HIP_CHECK(hipEventRecord(ev_io_[0], consumer));
+  PE_HIP_CHECK(hipStreamWaitEvent(stream_, ev_io_[0], 0));
+  enqueue_wflush();
+  dev::launch_gather_w(*kp_, dst, si, sj, off_i, off_j, stream_);
+  PE_HIP_CHECK(hipGetLastError());
+  PE_HIP_CHECK(hipEventRecord(ev_io_[1], stream_));
+  PE_HIP_CHECK(hipStreamWaitEvent(consumer, ev_io_[1], 0));
+}
+
 int64_t DeviceSolver::field_rows() const { return fused_ ? blk_.nx + 4 : blk_.rows; }
 int64_t DeviceSolver::field_cols() const { return fused_ ? geo_.plane : blk_.pitch; }
 
@@ -1449,7 +1546,7 @@ SolveResult device_solve_group(const Problem& P, int ranks, DecompMode mode, con
 }
 
 SolveResult device_solve_group(const Problem& P, const ProcessGrid& pg, const SolveOptions& opt,
-                               std::vector<double>* w_out, const UserFields& uf) {
+                               std::vector<double>* w_out, const UserFields& uf, const DeviceFields& df) {
   const auto t_start = clk::now();
   const int ranks = pg.Px * pg.Py;
   std::vector<std::unique_ptr<DeviceSolver>> s;
@@ -1457,8 +1554,10 @@ SolveResult device_solve_group(const Problem& P, const ProcessGrid& pg, const So
   for (int r = 0; r < ranks; ++r) {
     blks.push_back(decompose(P.M, P.N, pg, r));
     s.push_back(std::make_unique<DeviceSolver>(P, blks.back(), nullptr, opt));
-    if (uf.rhs) s.back()->set_rhs(block_field(uf.rhs, P.M, P.N, blks.back(), 0).data());
-    if (uf.w0) s.back()->set_w0(block_field(uf.w0, P.M, P.N, blks.back(), 1).data());
+    if (df.rhs) s.back()->set_rhs_device(df.rhs, df.rhs_si, df.rhs_sj, df.rhs_f32, df.stream);
+    else if (uf.rhs) s.back()->set_rhs(block_field(uf.rhs, P.M, P.N, blks.back(), 0).data());
+    if (df.w0) s.back()->set_w0_device(df.w0, df.w0_si, df.w0_sj, df.w0_f32, df.stream);
+    else if (uf.w0) s.back()->set_w0(block_field(uf.w0, P.M, P.N, blks.back(), 1).data());
   }
   const bool fused = s[0]->fused();
   // multi-step sweeps (three-step on blocks of >= 12 x 12): one launch per
@@ -1589,10 +1688,13 @@ SolveResult device_solve_group(const Problem& P, const ProcessGrid& pg, const So
   res.last_diff = hs.last_diff;
   res.zr = hs.rz_cur;
   if (opt.compute_error) {
-    res.l2_err = uf.rhs ? -1.0 : std::sqrt(hs.err[0] * P.h1() * P.h2());
-    res.max_err = uf.rhs ? -1.0 : hs.err[1];
+    res.l2_err = (uf.rhs || df.rhs) ? -1.0 : std::sqrt(hs.err[0] * P.h1() * P.h2());
+    res.max_err = (uf.rhs || df.rhs) ? -1.0 : hs.err[1];
     res.max_outside = hs.err[2];
   }
+  if (df.w_dst)  // every block into its position of the one global array
+    for (int r = 0; r < ranks; ++r)
+      s[r]->copy_w_device(df.w_dst, df.w_si, df.w_sj, blks[r].i0 - 1, blks[r].j0 - 1, df.stream);
   if (w_out) {
     const int64_t ny = P.N - 1;
     w_out->assign(size_t((P.M - 1) * ny), 0.0);

@@ -498,6 +498,43 @@ __global__ __launch_bounds__(TJ) void kInitField(KParams k, const double* __rest
   }
 }
 
+// A block's dense plane cut out of a global interior array in device memory
+// (DeviceSolver::set_rhs_device / set_w0_device): the device twin of
+// pe::block_field.  `g` is element [0][0] of the (gnx = M−1) × (gny = N−1)
+// array with element strides (si, sj) ≥ 0 (0: an expanded tensor); `out` is
+// rows × cols dense, rows = nx + 2 RING, cols = ny + 2 RING.  Local (li, lj)
+// is global (i0−1+li, j0−1+lj); the ring holds the neighbours' values and
+// exact zeros on the box boundary.  Flat grid-stride with lanes along j, so
+// sj == 1 reads and all writes are coalesced; float widens exactly.
+template <typename T, int RING>
+__global__ __launch_bounds__(256) void kSliceField(const T* __restrict__ g, int64_t si, int64_t sj, int64_t gnx,
+                                                   int64_t gny, int64_t i0, int64_t j0, int64_t rows, int64_t cols,
+                                                   double* __restrict__ out) {
+  const int64_t n = rows * cols;
+  for (int64_t idx = int64_t(blockIdx.x) * 256 + threadIdx.x; idx < n; idx += int64_t(gridDim.x) * 256) {
+    const int64_t a = idx / cols, b = idx - a * cols;
+    const int64_t gi = i0 + a - RING, gj = j0 + b - RING;  // global node, 1-based
+    double v = 0.0;
+    if (gi >= 1 && gi <= gnx && gj >= 1 && gj <= gny) v = double(g[(gi - 1) * si + (gj - 1) * sj]);
+    out[idx] = v;
+  }
+}
+
+// The owned nx × ny part of w (either layout: local (li, lj) at
+// w + li·wpitch + lj) into a destination with element strides (si, sj), at
+// element offset (off_i, off_j): (0, 0) for a dense block, (i0−1, j0−1) for
+// the block's position inside a global interior array
+// (DeviceSolver::copy_w_device, after the deferred w term is flushed).
+__global__ __launch_bounds__(256) void kGatherW(const double* __restrict__ w, int64_t wpitch, int64_t nx, int64_t ny,
+                                                double* __restrict__ dst, int64_t si, int64_t sj, int64_t off_i,
+                                                int64_t off_j) {
+  const int64_t n = nx * ny;
+  for (int64_t idx = int64_t(blockIdx.x) * 256 + threadIdx.x; idx < n; idx += int64_t(gridDim.x) * 256) {
+    const int64_t li = idx / ny, lj = idx - li * ny;
+    dst[(off_i + li) * si + (off_j + lj) * sj] = w[(li + 1) * wpitch + lj + 1];
+  }
+}
+
 // Error against the analytic solution u = F(1 - cx x² - cy y²)/(2cx + 2cy).
 __global__ __launch_bounds__(TJ) void kError(KParams k) {
   __shared__ double sm[8];
@@ -758,6 +795,26 @@ void launch_copy_words(void* dst, const void* src, size_t bytes, bool to_host, h
   const unsigned g = unsigned(std::min<int64_t>(1024, (n + 255) / 256));
   hipLaunchKernelGGL(kCopyWords, dim3(g), dim3(256), 0, s, static_cast<const unsigned*>(src),
                      static_cast<unsigned*>(dst), n, to_host ? 1 : 0);
+}
+
+static unsigned copy_blocks(int64_t n) { return unsigned(std::max<int64_t>(1, std::min<int64_t>(4096, (n + 255) / 256))); }
+
+void launch_slice_field(const void* g, bool f32, int64_t si, int64_t sj, int64_t gnx, int64_t gny, int64_t i0,
+                        int64_t j0, int64_t nx, int64_t ny, int ring, double* out, hipStream_t s) {
+  const int64_t rows = nx + 2 * ring, cols = ny + 2 * ring;
+  const dim3 grid(copy_blocks(rows * cols)), block(256);
+  const float* gf = static_cast<const float*>(g);
+  const double* gd = static_cast<const double*>(g);
+  if (f32 && ring) hipLaunchKernelGGL((kSliceField<float, 1>), grid, block, 0, s, gf, si, sj, gnx, gny, i0, j0, rows, cols, out);
+  else if (f32) hipLaunchKernelGGL((kSliceField<float, 0>), grid, block, 0, s, gf, si, sj, gnx, gny, i0, j0, rows, cols, out);
+  else if (ring) hipLaunchKernelGGL((kSliceField<double, 1>), grid, block, 0, s, gd, si, sj, gnx, gny, i0, j0, rows, cols, out);
+  else hipLaunchKernelGGL((kSliceField<double, 0>), grid, block, 0, s, gd, si, sj, gnx, gny, i0, j0, rows, cols, out);
+}
+
+void launch_gather_w(const KParams& k, double* dst, int64_t si, int64_t sj, int64_t off_i, int64_t off_j,
+                     hipStream_t s) {
+  hipLaunchKernelGGL(kGatherW, dim3(copy_blocks(k.nx * k.ny)), dim3(256), 0, s, k.w, k.wpitch, k.nx, k.ny, dst, si, sj,
+                     off_i, off_j);
 }
 
 void launch_error(const KParams& k, hipStream_t s) {

@@ -298,6 +298,15 @@ void launch_init(const KParams& k, int init_random, unsigned long long seed, dou
 // w0 dense (nx+2) × (ny+2) with its ring; w0 overrides init_random.
 void launch_init_field(const KParams& k, const double* rhs, const double* w0, int init_random,
                        unsigned long long seed, double amp, int variant, hipStream_t s);
+// kSliceField: block (i0, j0, nx, ny)'s dense plane (ring 0: nx × ny, ring 1:
+// (nx+2) × (ny+2) with the neighbours' values / box-boundary zeros) out of a
+// global interior array gnx × gny in device memory, element strides (si, sj)
+// ≥ 0, float64 or (f32) float32.  The device twin of pe::block_field.
+void launch_slice_field(const void* g, bool f32, int64_t si, int64_t sj, int64_t gnx, int64_t gny, int64_t i0,
+                        int64_t j0, int64_t nx, int64_t ny, int ring, double* out, hipStream_t s);
+// kGatherW: the owned w → dst[(off_i + li) si + (off_j + lj) sj], li < nx, lj < ny (after the w flush).
+void launch_gather_w(const KParams& k, double* dst, int64_t si, int64_t sj, int64_t off_i, int64_t off_j,
+                     hipStream_t s);
 void launch_F(const KParams& k, int par, int variant, hipStream_t s);
 void launch_G(const KParams& k, int par, int variant, hipStream_t s);
 void launch_error(const KParams& k, hipStream_t s);

@@ -156,6 +156,21 @@ class DeviceSolver {
   // and ignores w0.
   void set_rhs(const double* owned);
   void set_w0(const double* ringed);
+  // The same fields from device memory: `g` points at element [0][0] of the
+  // GLOBAL interior array (M-1) × (N-1) on this solver's device, float64 or
+  // (f32) float32, element strides (si, sj) ≥ 0 (0: an expanded tensor).  This
+  // block's share is cut out by kSliceField into the same planes set_rhs /
+  // set_w0 fill; nullptr clears the field.  Ordered by events, no host
+  // synchronise: the solver stream waits for what `producer` has enqueued so
+  // far, and `producer` waits for the slice — the caller may overwrite or free
+  // the array in `producer`'s order as soon as the call returns.  Anything but
+  // device memory of the solver's device (first and last element) throws
+  // std::invalid_argument before any launch and leaves the field as it was.
+  void set_rhs_device(const void* g, int64_t si, int64_t sj, bool f32, hipStream_t producer);
+  void set_w0_device(const void* g, int64_t si, int64_t sj, bool f32, hipStream_t producer);
+  // Host copy of the user plane (0: rhs, nx × ny; 1: w0, (nx+2) × (ny+2));
+  // empty when the field is unset.  Synchronizes the stream (tests).
+  std::vector<double> user_plane(int which);
   bool user_rhs() const { return rhs_dev_ != nullptr; }
   bool user_w0() const { return w0_dev_ != nullptr; }
   // Tuning probe: re-lay out the work items for `ti` rows per item, re-reading
@@ -265,6 +280,13 @@ class DeviceSolver {
   // State / data access.
   void read_state(dev::DevState* out);
   void copy_w(double* host, bool owned_only = true);  // nx × ny row-major
+  // The owned w into device memory of this solver's device (kGatherW):
+  // dst[(off_i + li) si + (off_j + lj) sj], li < nx, lj < ny — offsets (0, 0)
+  // for a dense nx × ny array, (i0-1, j0-1) for the block's position inside a
+  // global interior array.  Events only: the solver stream waits for
+  // `consumer` (the destination may have work pending from its allocator's
+  // stream), `consumer` waits for the gather.  Same pointer check as set_*_device.
+  void copy_w_device(double* dst, int64_t si, int64_t sj, int64_t off_i, int64_t off_j, hipStream_t consumer);
   // 0 r, 1 w, 2 p0, 3 p1 (single-sweep: 0 r of x[0], 2 p of x[0], 3 p of
   // x[1], 4 r of x[1]) as field_rows() × field_cols(), local (-h, -h) first.
   void copy_field(int which, double* host);
@@ -283,6 +305,12 @@ class DeviceSolver {
   void build_tables(int64_t rows_hi, int64_t cols_hi);
   void upload(void* dst, const void* src, size_t bytes);  // set-up data via pinned staging + copy kernel
   void set_plane(double** plane, const double* host, int64_t n);  // set_rhs / set_w0
+  // set_rhs_device / set_w0_device (ring 0 / 1)
+  void set_plane_device(double** plane, int ring, const void* g, int64_t si, int64_t sj, bool f32, hipStream_t producer,
+                        const char* what);
+  // throws std::invalid_argument unless elements [0] and [last] of `p` are device memory of device_
+  void check_device_span(const void* p, int64_t last, size_t elem, const char* what) const;
+  void io_events();  // creates ev_io_ on first use
   void set_fused_fields(double* x0, double* x1, double* w);
   // item lists at `ti` rows per item: static layout or dynamic per-XCD shards (+ halo/interior overlap)
   void apply_layout(int ti);
@@ -359,6 +387,8 @@ class DeviceSolver {
   int64_t hsize_ = 0;
   double* rhs_dev_ = nullptr;  // user right-hand side, dense nx × ny (null: F)
   double* w0_dev_ = nullptr;   // user initial guess, dense (nx+2) × (ny+2) with its ring (null: opt_.init)
+  int device_ = 0;             // the device the solver was constructed on (device fields must live there)
+  hipEvent_t ev_io_[2] = {nullptr, nullptr};  // device fields: caller's stream → solver stream, and back
   double* partial_ = nullptr;
   double* hist_ = nullptr;
   unsigned long long* stamps_ = nullptr;
@@ -447,9 +477,26 @@ class DeviceSolver {
 // device-to-device copies + a cross-stream reduction kernel.
 // `fields`: user right-hand side / initial guess as global interior arrays;
 // every block takes its slices through block_field (pe/fields.hpp).
+// `dfields`: the same fields, and a destination for w, as global interior
+// arrays in device memory (the sibling of UserFields; a field given both ways
+// is taken from the device).  Every block's solver slices its part with
+// set_*_device and gathers its w into its position of `w_dst` with
+// copy_w_device, ordered with `stream` by events.
+struct DeviceFields {
+  const void* rhs = nullptr;  // element [0][0], strides in elements, float64 or float32
+  int64_t rhs_si = 0, rhs_sj = 0;
+  bool rhs_f32 = false;
+  const void* w0 = nullptr;
+  int64_t w0_si = 0, w0_sj = 0;
+  bool w0_f32 = false;
+  double* w_dst = nullptr;    // (M-1) × (N-1), strides in elements
+  int64_t w_si = 0, w_sj = 0;
+  hipStream_t stream = nullptr;  // the caller's stream (producer of the fields, consumer of w)
+};
 SolveResult device_solve_group(const Problem& prob, int ranks, DecompMode mode, const SolveOptions& opt,
                                std::vector<double>* w_out = nullptr, const UserFields& fields = UserFields());
 SolveResult device_solve_group(const Problem& prob, const ProcessGrid& pg, const SolveOptions& opt,
-                               std::vector<double>* w_out = nullptr, const UserFields& fields = UserFields());
+                               std::vector<double>* w_out = nullptr, const UserFields& fields = UserFields(),
+                               const DeviceFields& dfields = DeviceFields());
 
 }  // namespace pe

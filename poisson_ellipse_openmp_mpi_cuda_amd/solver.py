@@ -81,6 +81,9 @@ class SolveReport:
     res_gap: float = -1.0
     b_norm: float = -1.0
     restarts: int = 0
+    # return_w="device" on a multi-process hip job: w is this rank's owned block and (i0, j0) the global
+    # 1-based node index of its first entry (None: w is the global array)
+    w_origin: Optional[tuple] = None
 
     @property
     def iters_per_s(self) -> float:
@@ -88,7 +91,7 @@ class SolveReport:
         return self.iters / t if t > 0 else 0.0
 
     def to_dict(self) -> dict:
-        d = dataclasses.asdict(self)
+        d = dataclasses.asdict(dataclasses.replace(self, w=None))  # (w, array or device tensor, is not copied)
         d.pop("w", None)
         d["iters_per_s"] = self.iters_per_s
         return d
@@ -125,6 +128,8 @@ def user_field(name: str, f, prob: EllipseProblem) -> Optional[np.ndarray]:
     (wider floats, large integers, complex, non-numeric), non-finite values."""
     if f is None:
         return None
+    if is_device_tensor(f):  # (the host path: one device → host copy)
+        f = f.detach().cpu()
     if hasattr(f, "detach") and hasattr(f, "numpy"):  # a CPU torch tensor
         f = f.detach().numpy()
     a = np.asarray(f)
@@ -138,6 +143,59 @@ def user_field(name: str, f, prob: EllipseProblem) -> Optional[np.ndarray]:
     if not np.isfinite(out).all():
         raise ValueError(f"{name}: non-finite values")
     return out
+
+
+def is_device_tensor(f) -> bool:
+    """A torch tensor in GPU memory (what the hip backends take without a host copy)."""
+    return hasattr(f, "data_ptr") and bool(getattr(f, "is_cuda", False))
+
+
+def tensor_spec(name: str, t, prob: EllipseProblem):
+    """(address of element [0, 0], stride_i, stride_j, is_float32) of a torch
+    tensor holding a global interior field — what DeviceSolver.set_rhs_device /
+    set_w0_device take.  Strides are in elements; any are accepted (a
+    transposed view, a window of a larger tensor, 0 for an expanded one).
+    ValueError: a shape other than (M-1, N-1), a dtype other than float64 /
+    float32."""
+    import torch
+
+    if t.dtype not in (torch.float64, torch.float32):
+        raise ValueError(f"{name}: dtype {t.dtype} on the device must be torch.float64 or torch.float32")
+    if tuple(t.shape) != (prob.M - 1, prob.N - 1):
+        raise ValueError(f"{name}: expected the global interior, shape {(prob.M - 1, prob.N - 1)}, got {tuple(t.shape)}")
+    si, sj = t.stride()
+    return int(t.data_ptr()), int(si), int(sj), t.dtype == torch.float32
+
+
+def device_field(name: str, f, prob: EllipseProblem, index: int):
+    """tensor_spec of a GPU tensor for a solver running on cuda:`index`, after
+    the checks of the host path: ValueError for a tensor on another device
+    and for non-finite values (torch.isfinite over the whole global tensor, so
+    every rank of a multi-process job decides alike without a collective)."""
+    import torch
+
+    t = f.detach()
+    spec = tensor_spec(name, t, prob)
+    if not t.is_cuda or t.device.index != index:
+        raise ValueError(f"{name}: tensor on {t.device}, the solver runs on cuda:{index}")
+    if not bool(torch.isfinite(t).all()):
+        raise ValueError(f"{name}: non-finite values")
+    return spec
+
+
+def _field_arg(name, f, prob, on_device: bool):
+    """A user field as solve() hands it on: None, a checked float64 host array,
+    or (hip backends) the GPU tensor itself, checked where its device is known."""
+    if on_device and is_device_tensor(f):
+        tensor_spec(name, f, prob)  # shape / dtype now; device and values once the solver's device is known
+        return f
+    return user_field(name, f, prob)
+
+
+def _stream_handle(index: int) -> int:
+    import torch
+
+    return int(torch.cuda.current_stream(index).cuda_stream)
 
 
 def _report(backend, prob, res, ranks, threads, init, w=None, rank=0) -> SolveReport:
@@ -155,8 +213,8 @@ def _report(backend, prob, res, ranks, threads, init, w=None, rank=0) -> SolveRe
 
 
 def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: int = 1, decomp: str | None = None,
-          init: str = "zero", seed: int = 1234, return_w: bool = False, device: str = "cuda", rhs=None, w0=None,
-          **kw) -> SolveReport:
+          init: str = "zero", seed: int = 1234, return_w: bool | str = False, device: str = "cuda", rhs=None,
+          w0=None, **kw) -> SolveReport:
     """Solve the fictitious-domain Poisson problem with the chosen backend.
 
     ``rhs`` / ``w0`` (every backend): a user right-hand side and initial guess
@@ -170,14 +228,35 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
     needs the same ``rhs`` again and ignores ``w0``.  None keeps the built-in
     constant F / ``init`` path bit for bit.
 
+    GPU tensors: on ``hip`` and ``hip-group`` either field may also be a torch
+    tensor in GPU memory — float64 or float32, shape (M-1, N-1), any strides,
+    on the device the solver runs on (cuda:0 for one process, the local
+    rank's device otherwise).  The solver cuts its planes out of it on the
+    device, ordered by events with ``torch.cuda.current_stream()``: no host
+    copy, and the tensor may be overwritten or freed in that stream's order as
+    soon as solve() returns.  The same values give the same bits as a host
+    array.  Host arrays and GPU tensors may be mixed.  Every other backend
+    copies a GPU tensor to the host first.  ``return_w="device"`` (``hip`` /
+    ``hip-group`` only) returns ``w`` as a float64 GPU tensor written by the
+    solver: the global array, or on a multi-process job this rank's owned
+    block, with ``w_origin = (i0, j0)`` the global 1-based node index of its
+    first entry (no gather).  DeviceSession keeps one constructed solver for a
+    sequence of such solves.
+
     For ``hip`` with torch.distributed initialised and world > 1 this is the
     per-rank call of a multi-GPU job (every rank calls it; rank 0's report
     carries the max-over-ranks timers and, with return_w, the gathered w).
     """
     if backend not in BACKENDS:
         raise ValueError(f"backend must be one of {BACKENDS}")
-    rhs = user_field("rhs", rhs, prob)
-    w0 = user_field("w0", w0, prob)
+    on_device = backend in ("hip", "hip-group")
+    if isinstance(return_w, str):
+        if return_w != "device":
+            raise ValueError('return_w must be True, False or "device"')
+        if not on_device:
+            raise ValueError(f'return_w="device" needs backend "hip" or "hip-group", not "{backend}"')
+    rhs = _field_arg("rhs", rhs, prob, on_device)
+    w0 = _field_arg("w0", w0, prob, on_device)
     if w0 is not None:
         init = "field"
     decomp = decomp or _decomp.default_spec(backend)
@@ -209,8 +288,25 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
         opt = _options(init, seed, chunk=kw.get("chunk", 0), timing=kw.get("timing", False),
                        variant=kw.get("variant", 0), check_tol=kw.get("check_tol", True),
                        algo=kw.get("algo", "auto"))
-        res, w = nat.device_solve_group_grid(P, _decomp.grid(ranks, prob.M, prob.N, decomp), opt, return_w, rhs, w0)
-        return _report(backend, prob, res, ranks, 1, init, None if w is None else np.asarray(w))
+        pg = _decomp.grid(ranks, prob.M, prob.N, decomp)
+        if not (is_device_tensor(rhs) or is_device_tensor(w0) or return_w == "device"):
+            res, w = nat.device_solve_group_grid(P, pg, opt, return_w, rhs, w0)
+            return _report(backend, prob, res, ranks, 1, init, None if w is None else np.asarray(w))
+        import torch
+
+        index = nat.current_device()  # the virtual ranks run on the process's current device
+        dev = {n: device_field(n, f, prob, index) for n, f in (("rhs", rhs), ("w0", w0)) if is_device_tensor(f)}
+        host = {n: f for n, f in (("rhs", rhs), ("w0", w0)) if n not in dev}
+        wt = w_dev = None
+        if return_w == "device":  # every block gathers into its position of this one tensor
+            wt = torch.empty((prob.M - 1, prob.N - 1), dtype=torch.float64, device=f"cuda:{index}")
+            w_dev = (wt.data_ptr(), wt.stride(0), wt.stride(1))
+        res, w = nat.device_solve_group_grid_device(P, pg, opt, bool(return_w) and wt is None, host.get("rhs"),
+                                                    host.get("w0"), dev.get("rhs"), dev.get("w0"), w_dev,
+                                                    _stream_handle(index))
+        if wt is None and w is not None:
+            wt = np.asarray(w)
+        return _report(backend, prob, res, ranks, 1, init, wt)
     # distributed backends
     from .parallel import dist as _dist
 
@@ -222,59 +318,135 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
         wg = _dist.gather_blocks(ctx, prob, blk, np.asarray(w)) if return_w else None
         return _report(backend, prob, res, ctx.world, threads, init, wg, ctx.rank)
     # hip
-    if nat.device_count() < 1:
-        raise RuntimeError("backend 'hip' needs a visible MI355X (HIP device)")
-    import torch.distributed as tdist
+    with DeviceSession(prob, decomp, init=init, seed=seed, **kw) as session:
+        return session._solve(rhs, w0, return_w)
 
-    if tdist.is_available() and tdist.is_initialized():
-        world = tdist.get_world_size()
-    else:
-        world = _dist.env_rank_world()[1]
-    opt = _options(init, seed, chunk=kw.get("chunk", 0), graph=kw.get("graph", False), timing=kw.get("timing", False),
-                   check_tol=kw.get("check_tol", True), variant=kw.get("variant", 0), algo=kw.get("algo", "auto"),
-                   checkpoint_every=kw.get("checkpoint_every", 0), checkpoint=kw.get("checkpoint"),
-                   resume=kw.get("resume"), keep_history=kw.get("keep_history", False),
-                   log_every=kw.get("log_every", 0))
-    if world == 1:
-        rank, comm = 0, None
-        nat.set_device(0)
-        blk = _decomp.block(prob.M, prob.N, 1, 0, decomp)
-    else:
-        ctx = _dist.init()
-        rank = ctx.rank
-        comm = _dist.rccl_comm(ctx)
-        blk = _decomp.block(prob.M, prob.N, world, rank, decomp)
-    solver = nat.DeviceSolver(P, blk, comm, opt)
-    try:
-        if rhs is not None or w0 is not None:  # this rank's slices of the global arrays
-            rhs_l, w0_l = nat.block_fields(prob.M, prob.N, blk, rhs, w0)
-            solver.set_rhs(rhs_l)
-            solver.set_w0(w0_l)
-        res = solver.solve()
-    except Exception:
-        if comm is not None:
-            _dist.drop_comm(comm)
-        raise
-    if comm is not None and (res.nonfinite or not np.isfinite(res.last_diff)):
-        _dist.drop_comm(comm)  # its P2P sequence may be out of step with the peers'
-    w = None
-    if return_w:
-        wl = np.asarray(solver.w())
-        if world == 1:
-            w = wl
+
+_HIP_OPTIONS = ("chunk", "graph", "timing", "check_tol", "variant", "algo", "checkpoint_every", "checkpoint", "resume",
+                "keep_history", "log_every")
+
+
+class DeviceSession:
+    """One constructed device solver (backend ``hip``) for a sequence of
+    solves: what ``solve(backend="hip")`` does up to and including the
+    construction of the native ``DeviceSolver`` — device, this rank's block,
+    the communicator of a multi-process job, the options — done once and kept.
+
+        with DeviceSession(prob) as s:
+            first = s.solve(rhs=f, return_w="device")
+            again = s.solve(rhs=1.01 * f, w0=first.w, return_w="device")
+
+    ``options`` are solve()'s for the ``hip`` backend (``init``, ``seed``,
+    ``algo``, ``check_tol``, ``graph``, ``chunk``, ...).  The construction time
+    is reported by the first solve only (``timers["construct"]`` is 0 after).
+    On a multi-process job every rank creates the session and calls solve()
+    with the same global fields, as with ``solve()``."""
+
+    def __init__(self, prob: EllipseProblem, decomp: str | None = None, **options):
+        nat = native()
+        if nat.device_count() < 1:
+            raise RuntimeError("backend 'hip' needs a visible MI355X (HIP device)")
+        import torch.distributed as tdist
+
+        from .parallel import dist as _dist
+
+        self.prob = prob
+        self.init = options.get("init", "zero")
+        decomp = decomp or _decomp.default_spec("hip")
+        if tdist.is_available() and tdist.is_initialized():
+            self.world = tdist.get_world_size()
         else:
-            w = _dist.gather_blocks(_dist.init(), prob, blk, wl)
-    rep = _report("hip", prob, res, world, 1, init, w, rank)
-    rep.comm = comm.name if comm is not None else "self"
-    rep.xr = bool(solver.xr)
-    rep.halo_push = bool(solver.halo_push)
-    rep.overlap = bool(solver.overlap)
-    rep.halo_put = bool(solver.halo_put)
-    rep.halo_path = str(solver.halo_path)
-    rep.halo_candidates = [[str(n), round(float(us), 2)] for n, us in solver.halo_candidates]
-    rep.put_status = str(solver.put_status)
-    rep.p2p_sum_setup = str(nat.p2p_setup_status())
-    rep.push_status = str(solver.push_status)
-    rep.sums = str(solver.xr_status)
-    rep.peer_access = [int(v) for v in solver.peer_access]
-    return rep
+            self.world = _dist.env_rank_world()[1]
+        opt = _options(self.init, options.get("seed", 1234), **{k: options[k] for k in _HIP_OPTIONS if k in options})
+        if self.world == 1:
+            self.rank, self.comm = 0, None
+            nat.set_device(0)
+            self.block = _decomp.block(prob.M, prob.N, 1, 0, decomp)
+        else:
+            ctx = _dist.init()
+            self.rank = ctx.rank
+            self.comm = _dist.rccl_comm(ctx)
+            self.block = _decomp.block(prob.M, prob.N, self.world, self.rank, decomp)
+        self.device_index = int(nat.current_device())  # device tensors must live here
+        self.solver = nat.DeviceSolver(prob.to_native(), self.block, self.comm, opt)
+
+    def close(self) -> None:
+        """Release the solver (its device memory and stream); idempotent."""
+        self.solver = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def solve(self, rhs=None, w0=None, return_w=False) -> SolveReport:
+        """One solve on the kept solver.  ``rhs`` / ``w0``: host arrays or GPU
+        tensors of the global interior, per call and mixed freely; None clears
+        a field back to F / ``init``.  ``return_w``: False, True (numpy; on a
+        multi-process job gathered onto rank 0) or "device" (a float64 GPU
+        tensor written by the solver; on a multi-process job this rank's block,
+        its position in the report's ``w_origin``)."""
+        if isinstance(return_w, str) and return_w != "device":
+            raise ValueError('return_w must be True, False or "device"')
+        return self._solve(_field_arg("rhs", rhs, self.prob, True), _field_arg("w0", w0, self.prob, True), return_w)
+
+    def _set_fields(self, rhs, w0) -> None:
+        """Both fields into the solver's planes; everything is checked before
+        anything is set, so a refused field leaves the solver as it was."""
+        nat, s, prob = native(), self.solver, self.prob
+        dev = {n: device_field(n, f, prob, self.device_index) for n, f in (("rhs", rhs), ("w0", w0))
+               if is_device_tensor(f)}
+        host = nat.block_fields(prob.M, prob.N, self.block, None if "rhs" in dev else rhs, None if "w0" in dev else w0)
+        stream = _stream_handle(self.device_index) if dev else 0
+        for n, local, set_host, set_dev in (("rhs", host[0], s.set_rhs, s.set_rhs_device),
+                                            ("w0", host[1], s.set_w0, s.set_w0_device)):
+            if n in dev:
+                set_dev(*dev[n], stream)
+            else:
+                set_host(local)  # (None clears)
+
+    def _solve(self, rhs, w0, return_w) -> SolveReport:
+        # rhs / w0: None, checked host arrays or GPU tensors of checked shape and dtype (_field_arg)
+        from .parallel import dist as _dist
+
+        if self.solver is None:
+            raise RuntimeError("DeviceSession is closed")
+        nat, s, prob, comm = native(), self.solver, self.prob, self.comm
+        try:
+            self._set_fields(rhs, w0)
+            res = s.solve()
+        except Exception:
+            if comm is not None:
+                _dist.drop_comm(comm)
+            raise
+        if comm is not None and (res.nonfinite or not np.isfinite(res.last_diff)):
+            _dist.drop_comm(comm)  # its P2P sequence may be out of step with the peers'
+        w = origin = None
+        if return_w == "device":
+            import torch
+
+            # single process: the block is the global interior; otherwise this rank's owned block
+            w = torch.empty((self.block.nx, self.block.ny), dtype=torch.float64, device=f"cuda:{self.device_index}")
+            s.copy_w_device(w.data_ptr(), w.stride(0), w.stride(1), 0, 0, _stream_handle(self.device_index))
+            if self.world > 1:
+                origin = (int(self.block.i0), int(self.block.j0))
+        elif return_w:
+            wl = np.asarray(s.w())
+            w = wl if self.world == 1 else _dist.gather_blocks(_dist.init(), prob, self.block, wl)
+        rep = _report("hip", prob, res, self.world, 1, "field" if w0 is not None else self.init, w, self.rank)
+        rep.w_origin = origin
+        rep.comm = comm.name if comm is not None else "self"
+        rep.xr = bool(s.xr)
+        rep.halo_push = bool(s.halo_push)
+        rep.overlap = bool(s.overlap)
+        rep.halo_put = bool(s.halo_put)
+        rep.halo_path = str(s.halo_path)
+        rep.halo_candidates = [[str(n), round(float(us), 2)] for n, us in s.halo_candidates]
+        rep.put_status = str(s.put_status)
+        rep.p2p_sum_setup = str(nat.p2p_setup_status())
+        rep.push_status = str(s.push_status)
+        rep.sums = str(s.xr_status)
+        rep.peer_access = [int(v) for v in s.peer_access]
+        return rep
