@@ -242,11 +242,12 @@ PYBIND11_MODULE(_native, m) {
   m.def(
       "cpu_solve_grid",
       [](const Problem& P, const ProcessGrid& pg, const SolveOptions& opt, bool return_w, py::object rhs,
-         py::object w0) {
-        FieldArr hr, hw;
+         py::object w0, py::object exact) {
+        FieldArr hr, hw, he;
         UserFields uf;
         uf.rhs = field_ptr(rhs, P.M - 1, P.N - 1, "rhs", hr);
         uf.w0 = field_ptr(w0, P.M - 1, P.N - 1, "w0", hw);
+        uf.exact = field_ptr(exact, P.M - 1, P.N - 1, "exact", he);
         std::vector<double> w;
         SolveResult r;
         {
@@ -258,7 +259,7 @@ PYBIND11_MODULE(_native, m) {
         return py::make_tuple(r, wa);
       },
       py::arg("prob"), py::arg("grid"), py::arg("opt") = SolveOptions(), py::arg("return_w") = false,
-      py::arg("rhs") = py::none(), py::arg("w0") = py::none());
+      py::arg("rhs") = py::none(), py::arg("w0") = py::none(), py::arg("exact") = py::none());
 
   // One rank of a multi-process CPU run; the transport is Python callbacks
   // (torch.distributed, typically gloo).  exchange_fn receives a list of
@@ -266,11 +267,13 @@ PYBIND11_MODULE(_native, m) {
   m.def(
       "cpu_solve_rank",
       [](const Problem& P, const Block& blk, py::function reduce_fn, py::function exchange_fn,
-         py::function barrier_fn, const SolveOptions& opt, bool return_w, py::object rhs, py::object w0) {
-        FieldArr hr, hw;
+         py::function barrier_fn, const SolveOptions& opt, bool return_w, py::object rhs, py::object w0,
+         py::object exact) {
+        FieldArr hr, hw, he;
         UserFields uf;  // the GLOBAL arrays: every rank passes the same and takes its slice
         uf.rhs = field_ptr(rhs, P.M - 1, P.N - 1, "rhs", hr);
         uf.w0 = field_ptr(w0, P.M - 1, P.N - 1, "w0", hw);
+        uf.exact = field_ptr(exact, P.M - 1, P.N - 1, "exact", he);
         auto reduce = [reduce_fn](double* buf, int n, bool is_max) {
           py::gil_scoped_acquire g;
           py::array_t<double> a({n}, {int64_t(sizeof(double))}, buf, py::none());
@@ -303,7 +306,7 @@ PYBIND11_MODULE(_native, m) {
       },
       py::arg("prob"), py::arg("block"), py::arg("reduce_fn"), py::arg("exchange_fn"), py::arg("barrier_fn"),
       py::arg("opt") = SolveOptions(), py::arg("return_w") = false, py::arg("rhs") = py::none(),
-      py::arg("w0") = py::none());
+      py::arg("w0") = py::none(), py::arg("exact") = py::none());
 
   // One block's slices of global interior arrays (pe/fields.hpp block_field):
   // (rhs owned nx × ny | None, w0 with its ring (nx+2) × (ny+2) | None) — the
@@ -320,6 +323,18 @@ PYBIND11_MODULE(_native, m) {
         return py::make_tuple(ro, wo);
       },
       py::arg("M"), py::arg("N"), py::arg("block"), py::arg("rhs") = py::none(), py::arg("w0") = py::none());
+
+  // One field's slice (ring 0: owned nx × ny, ring 1: with its ring) — the
+  // operand of DeviceSolver.set_exact (ring 0), and block_fields one field at a time.
+  m.def(
+      "block_field",
+      [](int M, int N, const Block& blk, py::object g, int ring) {
+        FieldArr h;
+        const double* p = field_ptr(g, int64_t(M) - 1, int64_t(N) - 1, "field", h);
+        if (!p) throw std::invalid_argument("block_field: the array is None");
+        return to_array(block_field(p, M, N, blk, ring), blk.nx + 2 * ring, blk.ny + 2 * ring);
+      },
+      py::arg("M"), py::arg("N"), py::arg("block"), py::arg("g"), py::arg("ring") = 0);
 
   m.def("host_coefficients", [](const Problem& P, const Block& blk) {
     std::vector<double> a, b;
@@ -557,6 +572,22 @@ PYBIND11_MODULE(_native, m) {
           py::arg("ptr"), py::arg("stride_i"), py::arg("stride_j"), py::arg("f32") = false, py::arg("stream") = 0,
           "the initial guess as the GLOBAL (M-1) × (N-1) array in device memory (see set_rhs_device)")
       .def(
+          "set_exact",
+          [](DeviceSolver& s, py::object owned) {
+            FieldArr h;
+            s.set_exact(field_ptr(owned, s.block().nx, s.block().ny, "exact", h));
+          },
+          py::arg("owned"),
+          "this block's nx × ny slice of the exact solution the error is taken against (block_field), or None for "
+          "the analytic one")
+      .def(
+          "set_exact_device",
+          [](DeviceSolver& s, uintptr_t ptr, int64_t si, int64_t sj, bool f32, uintptr_t stream) {
+            s.set_exact_device(reinterpret_cast<const void*>(ptr), si, sj, f32, reinterpret_cast<hipStream_t>(stream));
+          },
+          py::arg("ptr"), py::arg("stride_i"), py::arg("stride_j"), py::arg("f32") = false, py::arg("stream") = 0,
+          "the exact solution as the GLOBAL (M-1) × (N-1) array in device memory (see set_rhs_device)")
+      .def(
           "copy_w_device",
           [](DeviceSolver& s, uintptr_t ptr, int64_t si, int64_t sj, int64_t off_i, int64_t off_j, uintptr_t stream) {
             s.copy_w_device(reinterpret_cast<double*>(ptr), si, sj, off_i, off_j, reinterpret_cast<hipStream_t>(stream));
@@ -569,12 +600,13 @@ PYBIND11_MODULE(_native, m) {
           [](DeviceSolver& s, int which) -> py::object {
             std::vector<double> v = s.user_plane(which);
             if (v.empty()) return py::none();
-            const int64_t ring = which ? 1 : 0;
+            const int64_t ring = which == 1 ? 1 : 0;
             return to_array(std::move(v), s.block().nx + 2 * ring, s.block().ny + 2 * ring);
           },
-          py::arg("which"), "host copy of the user plane the solve reads (0 rhs, 1 w0), None when unset")
+          py::arg("which"), "host copy of the user plane the solve reads (0 rhs, 1 w0, 2 exact), None when unset")
       .def_property_readonly("user_rhs", &DeviceSolver::user_rhs)
       .def_property_readonly("user_w0", &DeviceSolver::user_w0)
+      .def_property_readonly("user_exact", &DeviceSolver::user_exact)
       .def("relayout", &DeviceSolver::relayout, py::arg("ti"), py::arg("order") = -1)
       .def("prepare_graphs",
            [](DeviceSolver& s, int64_t n) {
@@ -721,11 +753,12 @@ PYBIND11_MODULE(_native, m) {
   m.def(
       "device_solve_group_grid",
       [](const Problem& P, const ProcessGrid& pg, const SolveOptions& opt, bool return_w, py::object rhs,
-         py::object w0) {
-        FieldArr hr, hw;
+         py::object w0, py::object exact) {
+        FieldArr hr, hw, he;
         UserFields uf;
         uf.rhs = field_ptr(rhs, P.M - 1, P.N - 1, "rhs", hr);
         uf.w0 = field_ptr(w0, P.M - 1, P.N - 1, "w0", hw);
+        uf.exact = field_ptr(exact, P.M - 1, P.N - 1, "exact", he);
         std::vector<double> w;
         SolveResult r;
         {
@@ -737,10 +770,10 @@ PYBIND11_MODULE(_native, m) {
         return py::make_tuple(r, wa);
       },
       py::arg("prob"), py::arg("grid"), py::arg("opt") = SolveOptions(), py::arg("return_w") = false,
-      py::arg("rhs") = py::none(), py::arg("w0") = py::none());
+      py::arg("rhs") = py::none(), py::arg("w0") = py::none(), py::arg("exact") = py::none());
 
   // The same with fields and / or the result in device memory: rhs_dev /
-  // w0_dev = (address of element [0][0], stride_i, stride_j, float32 flag) of
+  // w0_dev / exact_dev = (address of element [0][0], stride_i, stride_j, float32 flag) of
   // the global interior array or None, w_dev = (address, stride_i, stride_j)
   // of a float64 (M-1) × (N-1) destination or None, `stream` the caller's
   // stream handle.  Host fields may be mixed in (a field given both ways is
@@ -748,11 +781,13 @@ PYBIND11_MODULE(_native, m) {
   m.def(
       "device_solve_group_grid_device",
       [](const Problem& P, const ProcessGrid& pg, const SolveOptions& opt, bool return_w, py::object rhs,
-         py::object w0, py::object rhs_dev, py::object w0_dev, py::object w_dev, uintptr_t stream) {
-        FieldArr hr, hw;
+         py::object w0, py::object rhs_dev, py::object w0_dev, py::object w_dev, uintptr_t stream, py::object exact,
+         py::object exact_dev) {
+        FieldArr hr, hw, he;
         UserFields uf;
         uf.rhs = field_ptr(rhs, P.M - 1, P.N - 1, "rhs", hr);
         uf.w0 = field_ptr(w0, P.M - 1, P.N - 1, "w0", hw);
+        uf.exact = field_ptr(exact, P.M - 1, P.N - 1, "exact", he);
         DeviceFields df;
         df.stream = reinterpret_cast<hipStream_t>(stream);
         if (!rhs_dev.is_none()) {
@@ -768,6 +803,13 @@ PYBIND11_MODULE(_native, m) {
           df.w0_si = std::get<1>(t);
           df.w0_sj = std::get<2>(t);
           df.w0_f32 = std::get<3>(t);
+        }
+        if (!exact_dev.is_none()) {
+          auto t = exact_dev.cast<std::tuple<uintptr_t, int64_t, int64_t, bool>>();
+          df.exact = reinterpret_cast<const void*>(std::get<0>(t));
+          df.exact_si = std::get<1>(t);
+          df.exact_sj = std::get<2>(t);
+          df.exact_f32 = std::get<3>(t);
         }
         if (!w_dev.is_none()) {
           auto t = w_dev.cast<std::tuple<uintptr_t, int64_t, int64_t>>();
@@ -787,7 +829,8 @@ PYBIND11_MODULE(_native, m) {
       },
       py::arg("prob"), py::arg("grid"), py::arg("opt") = SolveOptions(), py::arg("return_w") = false,
       py::arg("rhs") = py::none(), py::arg("w0") = py::none(), py::arg("rhs_dev") = py::none(),
-      py::arg("w0_dev") = py::none(), py::arg("w_dev") = py::none(), py::arg("stream") = 0);
+      py::arg("w0_dev") = py::none(), py::arg("w_dev") = py::none(), py::arg("stream") = 0,
+      py::arg("exact") = py::none(), py::arg("exact_dev") = py::none());
 
   // Single-shot device ops for numerics tests: `p` is a full local field
   // (rows × pitch, halo included); returns arrays of the same shape.

@@ -335,7 +335,9 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
         const double y = P.A2 + (blk.j0 - 1 + lj) * h2;
         const double wv = f.w[blk.at(li, lj)];
         if (in_ellipse(x, y, P.cx, P.cy)) {
-          const double u = P.u_scale() * (1.0 - P.cx * x * x - P.cy * y * y);
+          // (user exact solution: the global interior array at this node)
+          const double u = uf.exact ? uf.exact[(blk.i0 - 1 + li - 1) * (int64_t(P.N) - 1) + (blk.j0 - 1 + lj - 1)]
+                                    : P.u_scale() * (1.0 - P.cx * x * x - P.cy * y * y);
           const double e = wv - u;
           acc[0] += e * e;
           mx[0] = std::max(mx[0], std::fabs(e));
@@ -346,9 +348,10 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
     }
     comm.allreduce_sum(acc, 1);
     comm.allreduce_max(mx, 2);
-    // (a user right-hand side has no analytic solution here: -1)
-    res.l2_err = uf.rhs ? -1.0 : std::sqrt(acc[0] * h1 * h2);
-    res.max_err = uf.rhs ? -1.0 : mx[0];
+    // (a user right-hand side without a user exact solution has nothing to compare with: -1)
+    const bool no_exact = uf.rhs && !uf.exact;
+    res.l2_err = no_exact ? -1.0 : std::sqrt(acc[0] * h1 * h2);
+    res.max_err = no_exact ? -1.0 : mx[0];
     res.max_outside = mx[1];
   }
   if (w_out) {

@@ -576,6 +576,8 @@ void DeviceSolver::set_rhs(const double* owned) { set_plane(&rhs_dev_, owned, bl
 
 void DeviceSolver::set_w0(const double* ringed) { set_plane(&w0_dev_, ringed, (blk_.nx + 2) * (blk_.ny + 2)); }
 
+void DeviceSolver::set_exact(const double* owned) { set_plane(&exact_dev_, owned, blk_.nx * blk_.ny); }
+
 // Device memory of this solver's device at elements [0] and [last] of `p`
 // (hipPointerGetAttributes), and — where the runtime knows the allocation's
 // range — both inside one allocation.  Throws before anything is launched.
@@ -643,11 +645,15 @@ void DeviceSolver::set_w0_device(const void* g, int64_t si, int64_t sj, bool f32
   set_plane_device(&w0_dev_, 1, g, si, sj, f32, producer, "w0");
 }
 
+void DeviceSolver::set_exact_device(const void* g, int64_t si, int64_t sj, bool f32, hipStream_t producer) {
+  set_plane_device(&exact_dev_, 0, g, si, sj, f32, producer, "exact");
+}
+
 std::vector<double> DeviceSolver::user_plane(int which) {
-  if (which != 0 && which != 1) throw std::invalid_argument("user_plane: 0 (rhs) or 1 (w0)");
-  const double* plane = which ? w0_dev_ : rhs_dev_;
+  if (which < 0 || which > 2) throw std::invalid_argument("user_plane: 0 (rhs), 1 (w0) or 2 (exact)");
+  const double* plane = which == 1 ? w0_dev_ : which == 2 ? exact_dev_ : rhs_dev_;
   if (!plane) return {};
-  const int64_t ring = which;
+  const int64_t ring = which == 1;
   std::vector<double> v(size_t((blk_.nx + 2 * ring) * (blk_.ny + 2 * ring)));
   PE_HIP_CHECK(hipMemcpyAsync(v.data(), plane, sizeof(double) * v.size(), hipMemcpyDeviceToHost, stream_));
   PE_HIP_CHECK(hipStreamSynchronize(stream_));
@@ -727,6 +733,7 @@ DeviceSolver::~DeviceSolver() {
   if (stage_) (void)hipHostFree(stage_);
   if (rhs_dev_) (void)hipFree(rhs_dev_);
   if (w0_dev_) (void)hipFree(w0_dev_);
+  if (exact_dev_) (void)hipFree(exact_dev_);
   (void)hipFree(partial_);
   if (hist_) (void)hipFree(hist_);
   if (stamps_) (void)hipFree(stamps_);
@@ -879,7 +886,7 @@ void DeviceSolver::enqueue_G(int par) { dev::launch_G(*kp_, par, opt_.variant, s
 void DeviceSolver::enqueue_S(int par) { dev::launch_S(*kp_, par, stream_); }
 void DeviceSolver::enqueue_pack(int buf) { dev::launch_pack(*kp_, buf, stream_); }
 void DeviceSolver::enqueue_unpack(int buf) { dev::launch_unpack(*kp_, buf, stream_); }
-void DeviceSolver::enqueue_error() { dev::launch_error(*kp_, stream_); }
+void DeviceSolver::enqueue_error() { dev::launch_error(*kp_, stream_, exact_dev_); }
 
 // Cross-rank sum of sweep `par`'s 7 sums: nothing to enqueue when the sweep
 // sums them over ranks itself (k.xr, P2P transport).
@@ -1406,7 +1413,7 @@ SolveResult DeviceSolver::solve() {
   roctxRangePop();
 
   if (opt_.compute_error) {
-    dev::launch_error(*kp_, stream_);
+    dev::launch_error(*kp_, stream_, exact_dev_);
     comm_->allreduce_sum(st_->err, 1, stream_);
     comm_->allreduce_max(st_->err + 1, 2, stream_);
   }
@@ -1427,9 +1434,10 @@ SolveResult DeviceSolver::solve() {
   }
   res.zr = hs.rz_cur;
   if (opt_.compute_error) {
-    // (a user right-hand side has no analytic solution here: -1)
-    res.l2_err = rhs_dev_ ? -1.0 : std::sqrt(hs.err[0] * prob_.h1() * prob_.h2());
-    res.max_err = rhs_dev_ ? -1.0 : hs.err[1];
+    // (a user right-hand side without a user exact solution has nothing to compare with: -1)
+    const bool no_exact = rhs_dev_ && !exact_dev_;
+    res.l2_err = no_exact ? -1.0 : std::sqrt(hs.err[0] * prob_.h1() * prob_.h2());
+    res.max_err = no_exact ? -1.0 : hs.err[1];
     res.max_outside = hs.err[2];
   }
   // Per-phase totals: mean per sampled live iteration (samples taken after
@@ -1558,6 +1566,8 @@ SolveResult device_solve_group(const Problem& P, const ProcessGrid& pg, const So
     else if (uf.rhs) s.back()->set_rhs(block_field(uf.rhs, P.M, P.N, blks.back(), 0).data());
     if (df.w0) s.back()->set_w0_device(df.w0, df.w0_si, df.w0_sj, df.w0_f32, df.stream);
     else if (uf.w0) s.back()->set_w0(block_field(uf.w0, P.M, P.N, blks.back(), 1).data());
+    if (df.exact) s.back()->set_exact_device(df.exact, df.exact_si, df.exact_sj, df.exact_f32, df.stream);
+    else if (uf.exact) s.back()->set_exact(block_field(uf.exact, P.M, P.N, blks.back(), 0).data());
   }
   const bool fused = s[0]->fused();
   // multi-step sweeps (three-step on blocks of >= 12 x 12): one launch per
@@ -1688,8 +1698,9 @@ SolveResult device_solve_group(const Problem& P, const ProcessGrid& pg, const So
   res.last_diff = hs.last_diff;
   res.zr = hs.rz_cur;
   if (opt.compute_error) {
-    res.l2_err = (uf.rhs || df.rhs) ? -1.0 : std::sqrt(hs.err[0] * P.h1() * P.h2());
-    res.max_err = (uf.rhs || df.rhs) ? -1.0 : hs.err[1];
+    const bool no_exact = (uf.rhs || df.rhs) && !(uf.exact || df.exact);
+    res.l2_err = no_exact ? -1.0 : std::sqrt(hs.err[0] * P.h1() * P.h2());
+    res.max_err = no_exact ? -1.0 : hs.err[1];
     res.max_outside = hs.err[2];
   }
   if (df.w_dst)  // every block into its position of the one global array

@@ -535,8 +535,12 @@ __global__ __launch_bounds__(256) void kGatherW(const double* __restrict__ w, in
   }
 }
 
-// Error against the analytic solution u = F(1 - cx x² - cy y²)/(2cx + 2cy).
-__global__ __launch_bounds__(TJ) void kError(KParams k) {
+// Error against the analytic solution u = F(1 - cx x² - cy y²)/(2cx + 2cy),
+// or (FIELD) against the user's exact solution read from the dense nx × ny
+// plane `Up` (DeviceSolver::set_exact; values outside the ellipse are never
+// read).  Same walk, mask, block-ordered reduction and st->err slots either way.
+template <bool FIELD>
+__device__ __forceinline__ void error_body(const KParams& k, const double* Up) {
   __shared__ double sm[8];
   __shared__ int sflag;
   DevState* st = k.st;
@@ -547,7 +551,7 @@ __global__ __launch_bounds__(TJ) void kError(KParams k) {
     const double x = k.A1 + (k.gi0 + li) * k.h1, y = k.A2 + (k.gj0 + lj) * k.h2;
     const double wv = k.w[li * k.wpitch + lj];
     if (in_ellipse(x, y, k.cx, k.cy)) {
-      const double e = wv - k.u_scale * (1.0 - k.cx * x * x - k.cy * y * y);
+      const double e = wv - (FIELD ? Up[idx] : k.u_scale * (1.0 - k.cx * x * x - k.cy * y * y));
       e2 += e * e;
       emax = fmax(emax, fabs(e));
     } else {
@@ -583,6 +587,10 @@ __global__ __launch_bounds__(TJ) void kError(KParams k) {
       __hip_atomic_store(&st->ticket[3], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
   }
+}
+__global__ __launch_bounds__(TJ) void kError(KParams k) { error_body<false>(k, nullptr); }
+__global__ __launch_bounds__(TJ) void kErrorField(KParams k, const double* __restrict__ Up) {
+  error_body<true>(k, Up);
 }
 
 // True-residual check of a single-sweep-layout solve (DeviceSolver::residual_pass):
@@ -817,8 +825,9 @@ void launch_gather_w(const KParams& k, double* dst, int64_t si, int64_t sj, int6
                      off_i, off_j);
 }
 
-void launch_error(const KParams& k, hipStream_t s) {
-  hipLaunchKernelGGL(kError, dim3(flat_blocks(k)), dim3(TJ), 0, s, k);
+void launch_error(const KParams& k, hipStream_t s, const double* exact) {
+  if (exact) hipLaunchKernelGGL(kErrorField, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, exact);
+  else hipLaunchKernelGGL(kError, dim3(flat_blocks(k)), dim3(TJ), 0, s, k);
 }
 
 void launch_resid(const KParams& k, int bw, bool with_r, bool store, hipStream_t s, const double* rhs) {

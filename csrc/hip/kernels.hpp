@@ -309,7 +309,10 @@ void launch_gather_w(const KParams& k, double* dst, int64_t si, int64_t sj, int6
                      hipStream_t s);
 void launch_F(const KParams& k, int par, int variant, hipStream_t s);
 void launch_G(const KParams& k, int par, int variant, hipStream_t s);
-void launch_error(const KParams& k, hipStream_t s);
+// End-of-solve error → st->err = {Σ_D e², max_D |e|, max outside |w|}, e = w − u.
+// exact: the user exact solution's device plane (dense nx × ny; null: the
+// analytic u, kError).
+void launch_error(const KParams& k, hipStream_t s, const double* exact = nullptr);
 // True residual ρ = B − A w (w from the p-plane of x[bw], halo exchanged; r
 // from x[st->wpar] when with_r) → st->res; store: ρ → x[bw]'s r-plane.
 // rhs: the user right-hand side's device plane (dense nx × ny; null: F).

@@ -168,11 +168,23 @@ class DeviceSolver {
   // std::invalid_argument before any launch and leaves the field as it was.
   void set_rhs_device(const void* g, int64_t si, int64_t sj, bool f32, hipStream_t producer);
   void set_w0_device(const void* g, int64_t si, int64_t sj, bool f32, hipStream_t producer);
-  // Host copy of the user plane (0: rhs, nx × ny; 1: w0, (nx+2) × (ny+2));
-  // empty when the field is unset.  Synchronizes the stream (tests).
+  // User exact solution of the next solve()'s error (pe/fields.hpp): `owned`
+  // nx × ny (block_field ring 0) in host memory, or the global array in device
+  // memory, exactly like set_rhs / set_rhs_device.  While set, the end-of-solve
+  // error is taken against it (kErrorField) instead of the analytic solution,
+  // with or without a user rhs; it never enters the iteration.  The plane costs
+  // 8 B per owned node while set (allocated when set, freed when cleared) and
+  // survives reset() / solve() until replaced or cleared.  Not checkpointed: a
+  // resumed solve takes it again, as it takes rhs again.
+  void set_exact(const double* owned);
+  void set_exact_device(const void* g, int64_t si, int64_t sj, bool f32, hipStream_t producer);
+  // Host copy of the user plane (0: rhs, nx × ny; 1: w0, (nx+2) × (ny+2);
+  // 2: exact, nx × ny); empty when the field is unset.  Synchronizes the
+  // stream (tests).
   std::vector<double> user_plane(int which);
   bool user_rhs() const { return rhs_dev_ != nullptr; }
   bool user_w0() const { return w0_dev_ != nullptr; }
+  bool user_exact() const { return exact_dev_ != nullptr; }
   // Tuning probe: re-lay out the work items for `ti` rows per item, re-reading
   // the PE_* layout knobs (same allocation, so configurations compare at one
   // memory placement).  Drops cached graphs.
@@ -387,6 +399,7 @@ class DeviceSolver {
   int64_t hsize_ = 0;
   double* rhs_dev_ = nullptr;  // user right-hand side, dense nx × ny (null: F)
   double* w0_dev_ = nullptr;   // user initial guess, dense (nx+2) × (ny+2) with its ring (null: opt_.init)
+  double* exact_dev_ = nullptr;  // user exact solution, dense nx × ny (null: the analytic u)
   int device_ = 0;             // the device the solver was constructed on (device fields must live there)
   hipEvent_t ev_io_[2] = {nullptr, nullptr};  // device fields: caller's stream → solver stream, and back
   double* partial_ = nullptr;
@@ -475,7 +488,7 @@ class DeviceSolver {
 // P virtual ranks on ONE device (LocalComm).  Every rank runs the
 // same kernels and the same halo plan as under RCCL; the transport is
 // device-to-device copies + a cross-stream reduction kernel.
-// `fields`: user right-hand side / initial guess as global interior arrays;
+// `fields`: user right-hand side / initial guess / exact solution as global interior arrays;
 // every block takes its slices through block_field (pe/fields.hpp).
 // `dfields`: the same fields, and a destination for w, as global interior
 // arrays in device memory (the sibling of UserFields; a field given both ways
@@ -489,6 +502,9 @@ struct DeviceFields {
   const void* w0 = nullptr;
   int64_t w0_si = 0, w0_sj = 0;
   bool w0_f32 = false;
+  const void* exact = nullptr;
+  int64_t exact_si = 0, exact_sj = 0;
+  bool exact_f32 = false;
   double* w_dst = nullptr;    // (M-1) × (N-1), strides in elements
   int64_t w_si = 0, w_sj = 0;
   hipStream_t stream = nullptr;  // the caller's stream (producer of the fields, consumer of w)

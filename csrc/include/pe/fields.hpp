@@ -1,5 +1,5 @@
-// User fields of a solve: the right-hand side and the initial guess as arrays
-// over the global interior, and the one function that cuts a block's share
+// User fields of a solve: the right-hand side, the initial guess and the exact
+// solution as arrays over the global interior, and the one function that cuts a block's share
 // out of such an array (every backend and the Python binding slice with it).
 //
 // A global interior array is (M-1) × (N-1), row-major in i, entry
@@ -10,7 +10,12 @@
 //   w0:  the initial guess, r⁰ = B − A w⁰ (box-boundary values are 0; nodes
 //        outside the ellipse are unknowns of the fictitious-domain system and
 //        may start non-zero).  Overrides SolveOptions::init.
-// A null field keeps the built-in path (constant F / Init) bit for bit.
+//   exact: the solution to measure the end-of-solve error against, l2_err =
+//        sqrt(h1 h2 Σ_D (w − exact)²) and max_err = max_D |w − exact| over the
+//        nodes inside the ellipse (values outside are ignored).  It takes the
+//        place of the built-in analytic solution and never enters the solve.
+// A null field keeps the built-in path (constant F / Init / the analytic
+// error, or -1 with a user rhs) bit for bit.
 #pragma once
 
 #include <cstdint>
@@ -23,6 +28,7 @@ namespace pe {
 struct UserFields {
   const double* rhs = nullptr;
   const double* w0 = nullptr;
+  const double* exact = nullptr;
 };
 
 // Block `blk`'s share of the global interior array `g` of an M × N grid,

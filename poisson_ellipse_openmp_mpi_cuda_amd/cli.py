@@ -19,8 +19,14 @@ the dump of one run is a valid ``--w0`` of the next:
     python -m poisson_ellipse_openmp_mpi_cuda_amd.cli --rhs f.npy --dump w.npy 400 600
     python -m poisson_ellipse_openmp_mpi_cuda_amd.cli --rhs f.npy --w0 w.npy 400 600
 
-Checkpoints hold the iteration state, not the right-hand side: ``--resume``
-needs the same ``--rhs`` again, and ignores ``--w0``.
+``--exact FILE.npy`` (same form) is the solution the reported L2 / max error
+is measured against inside the ellipse, e.g. a manufactured u with
+``--rhs`` = −Δu; with ``--rhs`` alone the error line reads ``n/a``:
+
+    python -m poisson_ellipse_openmp_mpi_cuda_amd.cli --rhs f.npy --exact u.npy 400 600
+
+Checkpoints hold the iteration state, not the fields: ``--resume`` needs the
+same ``--rhs`` (and ``--exact``) again, and ignores ``--w0``.
 """
 
 from __future__ import annotations
@@ -52,11 +58,15 @@ def build_parser():
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--rhs", default=None, metavar="FILE.npy",
                     help="user right-hand side: float64 (M-1, N-1) array of the interior (masked by the ellipse; "
-                         "the L2 / max error against the analytic solution is then not reported); a resumed solve "
+                         "the L2 / max error is then reported only with --exact); a resumed solve "
                          "(--resume) needs the same --rhs again: checkpoints do not hold it")
     ap.add_argument("--w0", default=None, metavar="FILE.npy",
                     help="user initial guess: float64 (M-1, N-1) array, e.g. the --dump of an earlier run; "
                          "overrides --init; ignored with --resume")
+    ap.add_argument("--exact", default=None, metavar="FILE.npy",
+                    help="user exact solution: float64 (M-1, N-1) array the L2 / max error in D is measured against "
+                         "(in place of the analytic solution; values outside the ellipse are ignored); never enters "
+                         "the solve")
     ap.add_argument("--tol", type=float, default=1e-6)
     ap.add_argument("--max-iter", type=int, default=-1)
     ap.add_argument("--norm", choices=("weighted", "unweighted"), default="weighted")
@@ -90,18 +100,19 @@ def main(argv=None) -> int:
     try:
         rhs = None if a.rhs is None else user_field("--rhs", np.load(a.rhs, allow_pickle=False), prob)
         w0 = None if a.w0 is None else user_field("--w0", np.load(a.w0, allow_pickle=False), prob)
+        exact = None if a.exact is None else user_field("--exact", np.load(a.exact, allow_pickle=False), prob)
     except (OSError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 2
     rep = solve(prob, backend=a.backend, ranks=a.ranks, threads=a.threads, decomp=a.decomp, init=a.init,
                 seed=a.seed, return_w=want_w, variant=a.variant, timing=a.timing, graph=a.graph and not a.no_graph,
                 algo=a.algo, checkpoint=a.checkpoint, checkpoint_every=a.checkpoint_every, resume=a.resume,
-                log_every=a.log_every, rhs=rhs, w0=w0)
+                log_every=a.log_every, rhs=rhs, w0=w0, exact=exact)
     if rep.rank != 0:
         return 0
     if not a.quiet:
         print(legacy_lines(rep, a.tol))
-        if rhs is None:
+        if rhs is None or exact is not None:
             err = f"L2 error in D ~ {rep.l2_err:.6e} | max error in D ~ {rep.max_err:.6e}"
         else:
             err = "L2 error in D ~ n/a (user right-hand side)"

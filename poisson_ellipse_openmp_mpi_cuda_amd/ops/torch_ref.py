@@ -15,6 +15,8 @@ two_step / three_step) are INTERIOR arrays of shape (M-1, N-1), numpy or
 torch, entry [i-1, j-1] at node (x_i, y_j) — the shape every backend takes
 and ``return_w`` / ``--dump`` produce.  ``rhs`` is masked by the ellipse
 (B = rhs inside, 0 outside), ``w0`` starts the recurrence at r⁰ = B − A w⁰.
+pcg also takes ``exact``, the solution its l2_err / max_err are measured
+against inside the ellipse (it never enters the iteration).
 None keeps the built-in constant F / zero start bit for bit.  (pcg's older
 positional ``w0`` also still accepts a full (M+1, N+1) tensor.)
 """
@@ -155,9 +157,11 @@ def _start(prob, device, rhs, w0):
 
 
 def pcg(prob: EllipseProblem, device="cpu", w0=None, max_iter: Optional[int] = None,
-        keep_history: bool = False, *, rhs=None) -> TorchPCGResult:
+        keep_history: bool = False, *, rhs=None, exact=None) -> TorchPCGResult:
     """Reference-algorithm Jacobi PCG (stage2 solve_mpi order of operations).
-    With a user rhs the analytic solution does not apply: l2_err = max_err = -1."""
+    l2_err / max_err: against the user's `exact` when given, else against the
+    analytic solution; with a user rhs and no `exact` there is nothing to
+    compare with: -1."""
     a, b, B = assemble(prob, device, rhs=rhs)
     h1, h2 = prob.h1, prob.h2
     D = diag(a, b, h1, h2)
@@ -193,7 +197,10 @@ def pcg(prob: EllipseProblem, device="cpu", w0=None, max_iter: Optional[int] = N
         beta = zr_new / zr_old
         zr_old = zr_new
         p = z + beta * p
-    l2, mx = error_vs_analytic(prob, w) if rhs is None else (-1.0, -1.0)
+    if exact is not None:
+        l2, mx = error_vs_analytic(prob, w, embed(prob, exact, device))
+    else:
+        l2, mx = error_vs_analytic(prob, w) if rhs is None else (-1.0, -1.0)
     return TorchPCGResult(k, converged, w, l2, mx, hist)
 
 
@@ -439,12 +446,14 @@ def three_step(prob: EllipseProblem, sweeps: int, device="cpu", *, rhs=None, w0=
     return ThreeStepState(sweeps, sums, alphas, betas, diffs, r, p, w)
 
 
-def error_vs_analytic(prob: EllipseProblem, w: torch.Tensor):
-    """(L2 error in D, h-weighted; max error in D) against u = F(1-cx x²-cy y²)/(2cx+2cy)."""
+def error_vs_analytic(prob: EllipseProblem, w: torch.Tensor, u: Optional[torch.Tensor] = None):
+    """(L2 error in D, h-weighted; max error in D) against u = F(1-cx x²-cy y²)/(2cx+2cy),
+    or against a given u of w's shape (a user exact solution, embedded)."""
     x, y = _grid(prob, w.device)
     X = x[:, None]
     Y = y[None, :]
     inside = (prob.cx * X * X + prob.cy * Y * Y) < 1.0
-    u = prob.F / (2.0 * prob.cx + 2.0 * prob.cy) * (1.0 - prob.cx * X * X - prob.cy * Y * Y)
+    if u is None:
+        u = prob.F / (2.0 * prob.cx + 2.0 * prob.cy) * (1.0 - prob.cx * X * X - prob.cy * Y * Y)
     e = torch.where(inside, w - u, torch.zeros_like(w))[1:-1, 1:-1]
     return math.sqrt(float((e * e).sum()) * prob.h1 * prob.h2), float(e.abs().max())

@@ -122,7 +122,7 @@ def _options(init="zero", seed=1234, threads=1, chunk=0, graph=False, timing=Fal
 
 
 def user_field(name: str, f, prob: EllipseProblem) -> Optional[np.ndarray]:
-    """A user field (rhs / w0) as a C-contiguous float64 array of the global
+    """A user field (rhs / w0 / exact) as a C-contiguous float64 array of the global
     interior, shape (M-1, N-1), entry [i-1, j-1] at node (x_i, y_j) — or
     ValueError: wrong shape, data that float64 cannot hold without loss
     (wider floats, large integers, complex, non-numeric), non-finite values."""
@@ -153,7 +153,7 @@ def is_device_tensor(f) -> bool:
 def tensor_spec(name: str, t, prob: EllipseProblem):
     """(address of element [0, 0], stride_i, stride_j, is_float32) of a torch
     tensor holding a global interior field — what DeviceSolver.set_rhs_device /
-    set_w0_device take.  Strides are in elements; any are accepted (a
+    set_w0_device / set_exact_device take.  Strides are in elements; any are accepted (a
     transposed view, a window of a larger tensor, 0 for an expanded one).
     ValueError: a shape other than (M-1, N-1), a dtype other than float64 /
     float32."""
@@ -214,7 +214,7 @@ def _report(backend, prob, res, ranks, threads, init, w=None, rank=0) -> SolveRe
 
 def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: int = 1, decomp: str | None = None,
           init: str = "zero", seed: int = 1234, return_w: bool | str = False, device: str = "cuda", rhs=None,
-          w0=None, **kw) -> SolveReport:
+          w0=None, exact=None, **kw) -> SolveReport:
     """Solve the fictitious-domain Poisson problem with the chosen backend.
 
     ``rhs`` / ``w0`` (every backend): a user right-hand side and initial guess
@@ -223,12 +223,21 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
     returned ``w`` is a valid ``w0``.  B = rhs inside the ellipse and 0
     outside; r⁰ = B − A w⁰; ``w0`` overrides ``init`` (the report's ``init``
     is then "field").  With ``rhs`` the analytic solution does not apply and
-    ``l2_err`` / ``max_err`` are −1.  On multi-rank runs every rank passes the
-    same global arrays and takes its slice.  A resumed solve (``resume=``)
-    needs the same ``rhs`` again and ignores ``w0``.  None keeps the built-in
-    constant F / ``init`` path bit for bit.
+    ``l2_err`` / ``max_err`` are −1 unless ``exact`` is given.  On multi-rank
+    runs every rank passes the same global arrays and takes its slice.  A
+    resumed solve (``resume=``) needs the same ``rhs`` (and ``exact``) again
+    and ignores ``w0``.  None keeps the built-in constant F / ``init`` path bit
+    for bit.
 
-    GPU tensors: on ``hip`` and ``hip-group`` either field may also be a torch
+    ``exact`` (every backend, same form): the solution to report the error
+    against — a manufactured solution u with ``rhs`` = −Δu, say.  Then
+    ``l2_err`` = sqrt(h1·h2·Σ_D (w − exact)²) and ``max_err`` = max_D
+    |w − exact| over the nodes inside the ellipse, with or without ``rhs``
+    (it takes the place of the analytic solution); values outside the ellipse
+    are ignored.  It never enters the solve: iterations, ``w`` and every other
+    figure are those of the same call without it.
+
+    GPU tensors: on ``hip`` and ``hip-group`` any field may also be a torch
     tensor in GPU memory — float64 or float32, shape (M-1, N-1), any strides,
     on the device the solver runs on (cuda:0 for one process, the local
     rank's device otherwise).  The solver cuts its planes out of it on the
@@ -257,6 +266,7 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
             raise ValueError(f'return_w="device" needs backend "hip" or "hip-group", not "{backend}"')
     rhs = _field_arg("rhs", rhs, prob, on_device)
     w0 = _field_arg("w0", w0, prob, on_device)
+    exact = _field_arg("exact", exact, prob, on_device)
     if w0 is not None:
         init = "field"
     decomp = decomp or _decomp.default_spec(backend)
@@ -267,7 +277,7 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
         nranks = ranks if backend == "ranks" else 1
         opt = _options(init, seed, t, keep_history=kw.get("keep_history", False), log_every=kw.get("log_every", 0))
         res, w = nat.cpu_solve_grid(P, _decomp.grid(nranks, prob.M, prob.N, decomp if backend == "ranks" else "reference"),
-                                    opt, return_w, rhs, w0)
+                                    opt, return_w, rhs, w0, exact)
         return _report(backend, prob, res, nranks, t, init, None if w is None else np.asarray(w))
     if backend == "torch":
         import torch
@@ -277,7 +287,8 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
         if device.startswith("cuda") and not torch.cuda.is_available():
             device = "cpu"
         t0 = time.perf_counter()
-        r = torch_ref.pcg(prob, device=device, w0=w0, keep_history=kw.get("keep_history", False), rhs=rhs)
+        r = torch_ref.pcg(prob, device=device, w0=w0, keep_history=kw.get("keep_history", False), rhs=rhs,
+                          exact=exact)
         dt = time.perf_counter() - t0
         timers = dict(solver=dt, iterate=dt)
         return SolveReport("torch", prob.M, prob.N, 1, 1, 1, 1, r.iters, r.converged, False,
@@ -289,21 +300,22 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
                        variant=kw.get("variant", 0), check_tol=kw.get("check_tol", True),
                        algo=kw.get("algo", "auto"))
         pg = _decomp.grid(ranks, prob.M, prob.N, decomp)
-        if not (is_device_tensor(rhs) or is_device_tensor(w0) or return_w == "device"):
-            res, w = nat.device_solve_group_grid(P, pg, opt, return_w, rhs, w0)
+        if not (is_device_tensor(rhs) or is_device_tensor(w0) or is_device_tensor(exact) or return_w == "device"):
+            res, w = nat.device_solve_group_grid(P, pg, opt, return_w, rhs, w0, exact)
             return _report(backend, prob, res, ranks, 1, init, None if w is None else np.asarray(w))
         import torch
 
         index = nat.current_device()  # the virtual ranks run on the process's current device
-        dev = {n: device_field(n, f, prob, index) for n, f in (("rhs", rhs), ("w0", w0)) if is_device_tensor(f)}
-        host = {n: f for n, f in (("rhs", rhs), ("w0", w0)) if n not in dev}
+        fields = (("rhs", rhs), ("w0", w0), ("exact", exact))
+        dev = {n: device_field(n, f, prob, index) for n, f in fields if is_device_tensor(f)}
+        host = {n: f for n, f in fields if n not in dev}
         wt = w_dev = None
         if return_w == "device":  # every block gathers into its position of this one tensor
             wt = torch.empty((prob.M - 1, prob.N - 1), dtype=torch.float64, device=f"cuda:{index}")
             w_dev = (wt.data_ptr(), wt.stride(0), wt.stride(1))
         res, w = nat.device_solve_group_grid_device(P, pg, opt, bool(return_w) and wt is None, host.get("rhs"),
                                                     host.get("w0"), dev.get("rhs"), dev.get("w0"), w_dev,
-                                                    _stream_handle(index))
+                                                    _stream_handle(index), host.get("exact"), dev.get("exact"))
         if wt is None and w is not None:
             wt = np.asarray(w)
         return _report(backend, prob, res, ranks, 1, init, wt)
@@ -314,12 +326,12 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
         ctx = _dist.init()
         blk = _decomp.block(prob.M, prob.N, ctx.world, ctx.rank, decomp)
         opt = _options(init, seed, max(1, threads))
-        res, w = nat.cpu_solve_rank(P, blk, *_dist.gloo_callbacks(), opt, True, rhs, w0)
+        res, w = nat.cpu_solve_rank(P, blk, *_dist.gloo_callbacks(), opt, True, rhs, w0, exact)
         wg = _dist.gather_blocks(ctx, prob, blk, np.asarray(w)) if return_w else None
         return _report(backend, prob, res, ctx.world, threads, init, wg, ctx.rank)
     # hip
     with DeviceSession(prob, decomp, init=init, seed=seed, **kw) as session:
-        return session._solve(rhs, w0, return_w)
+        return session._solve(rhs, w0, return_w, exact)
 
 
 _HIP_OPTIONS = ("chunk", "graph", "timing", "check_tol", "variant", "algo", "checkpoint_every", "checkpoint", "resume",
@@ -381,41 +393,44 @@ class DeviceSession:
         self.close()
         return False
 
-    def solve(self, rhs=None, w0=None, return_w=False) -> SolveReport:
-        """One solve on the kept solver.  ``rhs`` / ``w0``: host arrays or GPU
-        tensors of the global interior, per call and mixed freely; None clears
-        a field back to F / ``init``.  ``return_w``: False, True (numpy; on a
+    def solve(self, rhs=None, w0=None, exact=None, return_w=False) -> SolveReport:
+        """One solve on the kept solver.  ``rhs`` / ``w0`` / ``exact``: host
+        arrays or GPU tensors of the global interior, per call and mixed
+        freely; None clears a field back to F / ``init`` / the analytic error.  ``return_w``: False, True (numpy; on a
         multi-process job gathered onto rank 0) or "device" (a float64 GPU
         tensor written by the solver; on a multi-process job this rank's block,
         its position in the report's ``w_origin``)."""
         if isinstance(return_w, str) and return_w != "device":
             raise ValueError('return_w must be True, False or "device"')
-        return self._solve(_field_arg("rhs", rhs, self.prob, True), _field_arg("w0", w0, self.prob, True), return_w)
+        return self._solve(_field_arg("rhs", rhs, self.prob, True), _field_arg("w0", w0, self.prob, True), return_w,
+                           _field_arg("exact", exact, self.prob, True))
 
-    def _set_fields(self, rhs, w0) -> None:
-        """Both fields into the solver's planes; everything is checked before
-        anything is set, so a refused field leaves the solver as it was."""
+    def _set_fields(self, rhs, w0, exact=None) -> None:
+        """The three fields into the solver's planes; everything is checked
+        before anything is set, so a refused field leaves the solver as it was."""
         nat, s, prob = native(), self.solver, self.prob
-        dev = {n: device_field(n, f, prob, self.device_index) for n, f in (("rhs", rhs), ("w0", w0))
+        dev = {n: device_field(n, f, prob, self.device_index) for n, f in (("rhs", rhs), ("w0", w0), ("exact", exact))
                if is_device_tensor(f)}
         host = nat.block_fields(prob.M, prob.N, self.block, None if "rhs" in dev else rhs, None if "w0" in dev else w0)
+        local_exact = None if "exact" in dev or exact is None else nat.block_field(prob.M, prob.N, self.block, exact, 0)
         stream = _stream_handle(self.device_index) if dev else 0
         for n, local, set_host, set_dev in (("rhs", host[0], s.set_rhs, s.set_rhs_device),
-                                            ("w0", host[1], s.set_w0, s.set_w0_device)):
+                                            ("w0", host[1], s.set_w0, s.set_w0_device),
+                                            ("exact", local_exact, s.set_exact, s.set_exact_device)):
             if n in dev:
                 set_dev(*dev[n], stream)
             else:
                 set_host(local)  # (None clears)
 
-    def _solve(self, rhs, w0, return_w) -> SolveReport:
-        # rhs / w0: None, checked host arrays or GPU tensors of checked shape and dtype (_field_arg)
+    def _solve(self, rhs, w0, return_w, exact=None) -> SolveReport:
+        # rhs / w0 / exact: None, checked host arrays or GPU tensors of checked shape and dtype (_field_arg)
         from .parallel import dist as _dist
 
         if self.solver is None:
             raise RuntimeError("DeviceSession is closed")
         nat, s, prob, comm = native(), self.solver, self.prob, self.comm
         try:
-            self._set_fields(rhs, w0)
+            self._set_fields(rhs, w0, exact)
             res = s.solve()
         except Exception:
             if comm is not None:
