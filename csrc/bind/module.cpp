@@ -50,6 +50,9 @@ py::array_t<double> to_array(std::vector<double>&& v, int64_t rows, int64_t cols
                              owner);
 }
 
+// (integral, energy, grad_max) of pe/fields.hpp GradStats
+py::tuple grad_tuple(const GradStats& g) { return py::make_tuple(g.integral, g.energy, g.grad_max); }
+
 py::dict state_dict(const dev::DevState& s) {
   py::dict d;
   d["red_F"] = py::make_tuple(s.red_F[0], s.red_F[1]);
@@ -102,6 +105,16 @@ const double* field_ptr(const py::object& o, int64_t rows, int64_t cols, const c
     throw std::invalid_argument(std::string(name) + ": expected shape (" + std::to_string(rows) + ", " +
                                 std::to_string(cols) + ")");
   return hold.data();
+}
+
+// A device field of Python, (address of element [0][0], stride_i, stride_j, float32 flag) or None, into DeviceFields.
+void device_spec(const py::object& o, const void*& ptr, int64_t& si, int64_t& sj, bool& f32) {
+  if (o.is_none()) return;
+  const auto t = o.cast<std::tuple<uintptr_t, int64_t, int64_t, bool>>();
+  ptr = reinterpret_cast<const void*>(std::get<0>(t));
+  si = std::get<1>(t);
+  sj = std::get<2>(t);
+  f32 = std::get<3>(t);
 }
 
 // Handle to a DeviceComm owned by Python.
@@ -217,6 +230,8 @@ PYBIND11_MODULE(_native, m) {
       .def_readonly("res_gap", &SolveResult::res_gap)
       .def_readonly("b_norm", &SolveResult::b_norm)
       .def_readonly("restarts", &SolveResult::restarts)
+      .def_property_readonly("grad", [](const SolveResult& r) { return grad_tuple(r.grad); },
+                             "(integral, energy, grad_max) where the solve computed them (hip-group on request), else -1s")
       .def_property_readonly("timers", [](const SolveResult& r) { return timers_dict(r.t); });
 
   m.def("format_result_legacy", &format_result_legacy);
@@ -335,6 +350,24 @@ PYBIND11_MODULE(_native, m) {
         return to_array(block_field(p, M, N, blk, ring), blk.nx + 2 * ring, blk.ny + 2 * ring);
       },
       py::arg("M"), py::arg("N"), py::arg("block"), py::arg("g"), py::arg("ring") = 0);
+
+  // The gradient of a global interior array and its functionals (pe/fields.hpp
+  // gradient_field): ((integral, energy, grad_max), g) with g of shape
+  // (2, M-1, N-1), [0] = ∂x, [1] = ∂y — or None with field=False.
+  m.def(
+      "gradient_field",
+      [](const Problem& P, py::object w, bool field) {
+        FieldArr h;
+        const double* p = field_ptr(w, int64_t(P.M) - 1, int64_t(P.N) - 1, "w", h);
+        if (!p) throw std::invalid_argument("gradient_field: the array is None");
+        const size_t n = size_t((int64_t(P.M) - 1) * (int64_t(P.N) - 1));
+        std::vector<double> g(field ? 2 * n : 0);
+        const GradStats s = gradient_field(P, p, field ? g.data() : nullptr, field ? g.data() + n : nullptr);
+        py::object ga = py::none();
+        if (field) ga = to_array(std::move(g), 2 * (int64_t(P.M) - 1), P.N - 1).attr("reshape")(2, P.M - 1, P.N - 1);
+        return py::make_tuple(grad_tuple(s), ga);
+      },
+      py::arg("prob"), py::arg("w"), py::arg("field") = true);
 
   m.def("host_coefficients", [](const Problem& P, const Block& blk) {
     std::vector<double> a, b;
@@ -596,6 +629,46 @@ PYBIND11_MODULE(_native, m) {
           py::arg("stream") = 0,
           "the owned w into float64 device memory at element offset (off_i, off_j) of `ptr`, ordered with `stream`")
       .def(
+          "gradient",
+          [](DeviceSolver& s, bool field) {
+            const Block& b = s.block();
+            std::vector<double> gx, gy;
+            if (field) {
+              gx.resize(size_t(b.nx * b.ny));
+              gy.resize(size_t(b.nx * b.ny));
+            }
+            GradStats g;
+            {
+              py::gil_scoped_release nogil;
+              g = s.gradient(field ? gx.data() : nullptr, field ? gy.data() : nullptr);
+            }
+            py::object ax = py::none(), ay = py::none();
+            if (field) {
+              ax = to_array(std::move(gx), b.nx, b.ny);
+              ay = to_array(std::move(gy), b.nx, b.ny);
+            }
+            return py::make_tuple(grad_tuple(g), ax, ay);
+          },
+          py::arg("field") = true,
+          "after solve(): ((integral, energy, grad_max), gx, gy) of w on this block's owned nodes (field=False: the "
+          "functionals only, gx = gy = None); collective on a multi-rank job; only reset() / solve() may follow")
+      .def(
+          "gradient_device",
+          [](DeviceSolver& s, uintptr_t gx, uintptr_t gy, int64_t si, int64_t sj, int64_t off_i, int64_t off_j,
+             uintptr_t stream) {
+            GradStats g;
+            {
+              py::gil_scoped_release nogil;
+              g = s.gradient_device(reinterpret_cast<double*>(gx), reinterpret_cast<double*>(gy), si, sj, off_i, off_j,
+                                    reinterpret_cast<hipStream_t>(stream));
+            }
+            return grad_tuple(g);
+          },
+          py::arg("gx"), py::arg("gy"), py::arg("stride_i"), py::arg("stride_j"), py::arg("off_i") = 0,
+          py::arg("off_j") = 0, py::arg("stream") = 0,
+          "the same with gx / gy written into float64 device memory at element offset (off_i, off_j), ordered with "
+          "`stream` (both addresses 0: the functionals only); returns (integral, energy, grad_max)")
+      .def(
           "user_plane",
           [](DeviceSolver& s, int which) -> py::object {
             std::vector<double> v = s.user_plane(which);
@@ -790,27 +863,9 @@ PYBIND11_MODULE(_native, m) {
         uf.exact = field_ptr(exact, P.M - 1, P.N - 1, "exact", he);
         DeviceFields df;
         df.stream = reinterpret_cast<hipStream_t>(stream);
-        if (!rhs_dev.is_none()) {
-          auto t = rhs_dev.cast<std::tuple<uintptr_t, int64_t, int64_t, bool>>();
-          df.rhs = reinterpret_cast<const void*>(std::get<0>(t));
-          df.rhs_si = std::get<1>(t);
-          df.rhs_sj = std::get<2>(t);
-          df.rhs_f32 = std::get<3>(t);
-        }
-        if (!w0_dev.is_none()) {
-          auto t = w0_dev.cast<std::tuple<uintptr_t, int64_t, int64_t, bool>>();
-          df.w0 = reinterpret_cast<const void*>(std::get<0>(t));
-          df.w0_si = std::get<1>(t);
-          df.w0_sj = std::get<2>(t);
-          df.w0_f32 = std::get<3>(t);
-        }
-        if (!exact_dev.is_none()) {
-          auto t = exact_dev.cast<std::tuple<uintptr_t, int64_t, int64_t, bool>>();
-          df.exact = reinterpret_cast<const void*>(std::get<0>(t));
-          df.exact_si = std::get<1>(t);
-          df.exact_sj = std::get<2>(t);
-          df.exact_f32 = std::get<3>(t);
-        }
+        device_spec(rhs_dev, df.rhs, df.rhs_si, df.rhs_sj, df.rhs_f32);
+        device_spec(w0_dev, df.w0, df.w0_si, df.w0_sj, df.w0_f32);
+        device_spec(exact_dev, df.exact, df.exact_si, df.exact_sj, df.exact_f32);
         if (!w_dev.is_none()) {
           auto t = w_dev.cast<std::tuple<uintptr_t, int64_t, int64_t>>();
           df.w_dst = reinterpret_cast<double*>(std::get<0>(t));
@@ -831,6 +886,59 @@ PYBIND11_MODULE(_native, m) {
       py::arg("rhs") = py::none(), py::arg("w0") = py::none(), py::arg("rhs_dev") = py::none(),
       py::arg("w0_dev") = py::none(), py::arg("w_dev") = py::none(), py::arg("stream") = 0,
       py::arg("exact") = py::none(), py::arg("exact_dev") = py::none());
+
+  // The same with the gradient of the solution (pe/fields.hpp): grad = 1 the
+  // functionals only (the result's integral / energy / grad_max), 2 the field
+  // as well — into grad_dev = (address of gx, address of gy, stride_i,
+  // stride_j), two float64 (M-1) × (N-1) destinations in device memory, or
+  // else returned as a (2, M-1, N-1) array.  Returns (result, w, gradient).
+  m.def(
+      "device_solve_group_grad",
+      [](const Problem& P, const ProcessGrid& pg, const SolveOptions& opt, bool return_w, int grad, py::object rhs,
+         py::object w0, py::object exact, py::object rhs_dev, py::object w0_dev, py::object exact_dev, py::object w_dev,
+         py::object grad_dev, uintptr_t stream) {
+        if (grad != 1 && grad != 2) throw std::invalid_argument("grad: 1 (functionals) or 2 (field)");
+        FieldArr hr, hw, he;
+        UserFields uf;
+        uf.rhs = field_ptr(rhs, P.M - 1, P.N - 1, "rhs", hr);
+        uf.w0 = field_ptr(w0, P.M - 1, P.N - 1, "w0", hw);
+        uf.exact = field_ptr(exact, P.M - 1, P.N - 1, "exact", he);
+        DeviceFields df;
+        df.stream = reinterpret_cast<hipStream_t>(stream);
+        device_spec(rhs_dev, df.rhs, df.rhs_si, df.rhs_sj, df.rhs_f32);
+        device_spec(w0_dev, df.w0, df.w0_si, df.w0_sj, df.w0_f32);
+        device_spec(exact_dev, df.exact, df.exact_si, df.exact_sj, df.exact_f32);
+        if (!w_dev.is_none()) {
+          const auto t = w_dev.cast<std::tuple<uintptr_t, int64_t, int64_t>>();
+          df.w_dst = reinterpret_cast<double*>(std::get<0>(t));
+          df.w_si = std::get<1>(t);
+          df.w_sj = std::get<2>(t);
+        }
+        if (!grad_dev.is_none()) {
+          const auto t = grad_dev.cast<std::tuple<uintptr_t, uintptr_t, int64_t, int64_t>>();
+          df.grad_x = reinterpret_cast<double*>(std::get<0>(t));
+          df.grad_y = reinterpret_cast<double*>(std::get<1>(t));
+          df.grad_si = std::get<2>(t);
+          df.grad_sj = std::get<3>(t);
+        }
+        std::vector<double> w, g;
+        GroupGradient gg;
+        gg.stats = true;
+        gg.host = grad == 2 && grad_dev.is_none() ? &g : nullptr;
+        SolveResult r;
+        {
+          py::gil_scoped_release nogil;
+          r = device_solve_group(P, pg, opt, return_w ? &w : nullptr, uf, df, gg);
+        }
+        py::object wa = py::none(), ga = py::none();
+        if (return_w) wa = to_array(std::move(w), P.M - 1, P.N - 1);
+        if (gg.host) ga = to_array(std::move(g), 2 * (int64_t(P.M) - 1), P.N - 1).attr("reshape")(2, P.M - 1, P.N - 1);
+        return py::make_tuple(r, wa, ga);
+      },
+      py::arg("prob"), py::arg("grid"), py::arg("opt"), py::arg("return_w"), py::arg("grad"), py::arg("rhs") = py::none(),
+      py::arg("w0") = py::none(), py::arg("exact") = py::none(), py::arg("rhs_dev") = py::none(),
+      py::arg("w0_dev") = py::none(), py::arg("exact_dev") = py::none(), py::arg("w_dev") = py::none(),
+      py::arg("grad_dev") = py::none(), py::arg("stream") = 0);
 
   // Single-shot device ops for numerics tests: `p` is a full local field
   // (rows × pitch, halo included); returns arrays of the same shape.

@@ -1150,6 +1150,100 @@ void DeviceSolver::residual_pass(bool with_r, bool store) {
   PE_HIP_CHECK(hipGetLastError());
 }
 
+// The gradient pass, residual_pass's sequence: w (flushed) into a plane the
+// layout exchanges — the p-plane of x[0], or the classic r plane with its y
+// strips — that plane's halo exchange, then kGradField reading it through
+// (base, pitch).  The iteration state in that plane is gone afterwards.
+void DeviceSolver::enqueue_grad_stage() {
+  const KParams& k = *kp_;
+  scratch_used_ = true;
+  enqueue_wflush();
+  if (fused_) {
+    dev::launch_w_to_p(k, 0, stream_);
+    dev::launch_pack(k, 0, stream_);  // (no-op without a y neighbour)
+  } else {
+    dev::launch_w_to_r(k, stream_);
+  }
+}
+
+void DeviceSolver::enqueue_grad(double* gx, double* gy, int64_t si, int64_t sj, int64_t off_i, int64_t off_j) {
+  const KParams& k = *kp_;
+  if (fused_) {
+    dev::launch_grad_field(k, k.x[0] + k.poff, k.pitch, gx, gy, si, sj, off_i, off_j, stream_);
+  } else {
+    dev::launch_unpack_r(k, stream_);
+    dev::launch_grad_field(k, k.r, k.pitch, gx, gy, si, sj, off_i, off_j, stream_);
+  }
+  PE_HIP_CHECK(hipGetLastError());
+}
+
+double* DeviceSolver::res_dev() { return st_->res; }
+
+GradStats DeviceSolver::gradient_pass(double* gx, double* gy, int64_t si, int64_t sj, int64_t off_i, int64_t off_j) {
+  enqueue_grad_stage();
+  if (comm_->size() > 1) {
+    if (fused_) enqueue_exchange(0, false);
+    else comm_->exchange(halo_plan(), stream_);
+  }
+  enqueue_grad(gx, gy, si, sj, off_i, off_j);
+  if (comm_->size() > 1) {
+    comm_->allreduce_sum(st_->res, 2, stream_);
+    comm_->allreduce_max(st_->res + 2, 1, stream_);
+  }
+  DevState hs;
+  read_state(&hs);
+  const double hh = prob_.h1() * prob_.h2();
+  GradStats g;
+  g.integral = hh * hs.res[0];
+  g.energy = hh * hs.res[1];
+  g.grad_max = std::sqrt(hs.res[2]);
+  return g;
+}
+
+GradStats DeviceSolver::gradient(double* gx_host, double* gy_host) {
+  if ((gx_host == nullptr) != (gy_host == nullptr)) throw std::invalid_argument("gradient: gx and gy go together");
+  if (!gx_host) return gradient_pass(nullptr, nullptr, 0, 0, 0, 0);
+  const size_t n = size_t(blk_.nx * blk_.ny);
+  double* d = nullptr;
+  PE_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d), sizeof(double) * 2 * n));
+  GradStats g;
+  try {
+    g = gradient_pass(d, d + n, blk_.ny, 1, 0, 0);
+    PE_HIP_CHECK(hipMemcpyAsync(gx_host, d, sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
+    PE_HIP_CHECK(hipMemcpyAsync(gy_host, d + n, sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
+    PE_HIP_CHECK(hipStreamSynchronize(stream_));
+  } catch (...) {
+    (void)hipFree(d);
+    throw;
+  }
+  PE_HIP_CHECK(hipFree(d));
+  return g;
+}
+
+void DeviceSolver::check_grad_span(const double* gx, const double* gy, int64_t si, int64_t sj, int64_t off_i,
+                                   int64_t off_j) const {
+  if (!gx || !gy) throw std::invalid_argument("grad: null destination");
+  if (si < 0 || sj < 0 || off_i < 0 || off_j < 0) throw std::invalid_argument("grad: negative stride or offset");
+  // (each destination from its element [0][0] to this block's last element)
+  const int64_t last = (off_i + blk_.nx - 1) * si + (off_j + blk_.ny - 1) * sj;
+  check_device_span(gx, last, sizeof(double), "grad x");
+  check_device_span(gy, last, sizeof(double), "grad y");
+}
+
+GradStats DeviceSolver::gradient_device(double* gx, double* gy, int64_t si, int64_t sj, int64_t off_i, int64_t off_j,
+                                        hipStream_t consumer) {
+  if ((gx == nullptr) != (gy == nullptr)) throw std::invalid_argument("grad: gx and gy go together");
+  if (!gx) return gradient_pass(nullptr, nullptr, 0, 0, 0, 0);
+  check_grad_span(gx, gy, si, sj, off_i, off_j);
+  io_events();
+  PE_HIP_CHECK(hipEventRecord(ev_io_[0], consumer));
+  PE_HIP_CHECK(hipStreamWaitEvent(stream_, ev_io_[0], 0));
+  const GradStats g = gradient_pass(gx, gy, si, sj, off_i, off_j);
+  PE_HIP_CHECK(hipEventRecord(ev_io_[1], stream_));
+  PE_HIP_CHECK(hipStreamWaitEvent(consumer, ev_io_[1], 0));
+  return g;
+}
+
 void DeviceSolver::read_state(DevState* out) {
   PE_HIP_CHECK(hipMemcpyAsync(out, st_, sizeof(DevState), hipMemcpyDeviceToHost, stream_));
   PE_HIP_CHECK(hipStreamSynchronize(stream_));
@@ -1166,6 +1260,7 @@ void DeviceSolver::synchronize() {
 
 void DeviceSolver::reset() {
   par_ = 0;
+  scratch_used_ = false;
   enqueue_init();
   if (fused_) {
     // r⁰ (and p = 0) in x[0] → halos → sweep S_0 (z₀, A z₀ and their sums,
@@ -1182,6 +1277,8 @@ void DeviceSolver::reset() {
 }
 
 void DeviceSolver::run_iterations(int64_t iters, bool use_graph) {
+  if (scratch_used_)
+    throw std::logic_error("run_iterations after gradient(): the pass used an iteration plane as scratch; reset() or solve() first");
   // (the three-step sweep ends an n-iteration run with a partial sweep when
   // 3 ∤ n; the two-step sweep has none — its one-iteration sweep ends the
   // solve — so an odd count would run one iteration too many)
@@ -1226,6 +1323,7 @@ SolveResult DeviceSolver::solve() {
   if (!opt_.resume_path.empty()) {
     const auto tc = clk::now();
     load_checkpoint(opt_.resume_path + ".r" + std::to_string(blk_.rank));
+    scratch_used_ = false;  // (every plane comes from the file)
     copy_s += secs(tc, clk::now());
     DevState s0;
     read_state(&s0);
@@ -1554,7 +1652,8 @@ SolveResult device_solve_group(const Problem& P, int ranks, DecompMode mode, con
 }
 
 SolveResult device_solve_group(const Problem& P, const ProcessGrid& pg, const SolveOptions& opt,
-                               std::vector<double>* w_out, const UserFields& uf, const DeviceFields& df) {
+                               std::vector<double>* w_out, const UserFields& uf, const DeviceFields& df,
+                               const GroupGradient& gg) {
   const auto t_start = clk::now();
   const int ranks = pg.Px * pg.Py;
   std::vector<std::unique_ptr<DeviceSolver>> s;
@@ -1688,8 +1787,61 @@ SolveResult device_solve_group(const Problem& P, const ProcessGrid& pg, const So
     PE_HIP_CHECK(hipStreamSynchronize(s0));
     PE_HIP_CHECK(hipFree(dm));
   }
+  // The gradient (DeviceSolver::gradient's phases on every block): w into the
+  // plane the layout exchanges, the halo exchange of buffer 0, then every
+  // block's kGradField writes its position of the global arrays; Σ, Σ, max of
+  // the blocks' res slots through kGroupReduce.
+  const bool grad_field = gg.host || df.grad_x;
+  double* gbuf = nullptr;  // gx then gy of the global interior, when the host wants them
+  if (gg.stats || grad_field) {
+    if ((df.grad_x == nullptr) != (df.grad_y == nullptr)) throw std::invalid_argument("grad: gx and gy go together");
+    if (df.grad_x && gg.host) throw std::invalid_argument("grad: a host or a device destination, not both");
+    const int64_t gny = P.N - 1, gn = (int64_t(P.M) - 1) * gny;
+    if (gg.host) PE_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&gbuf), sizeof(double) * 2 * size_t(gn)));
+    std::vector<double*> hg(2 * ranks);
+    for (int r = 0; r < ranks; ++r) {
+      hg[r] = s[r]->res_dev();
+      hg[ranks + r] = s[r]->res_dev() + 2;
+    }
+    double** dg = nullptr;
+    PE_HIP_CHECK(hipMalloc(&dg, sizeof(double*) * 2 * ranks));
+    PE_HIP_CHECK(hipMemcpy(dg, hg.data(), sizeof(double*) * 2 * ranks, hipMemcpyHostToDevice));
+    if (df.grad_x) {  // the caller's arrays: checked before any launch, ordered with the caller's stream by events
+      for (int r = 0; r < ranks; ++r)
+        s[r]->check_grad_span(df.grad_x, df.grad_y, df.grad_si, df.grad_sj, blks[r].i0 - 1, blks[r].j0 - 1);
+      PE_HIP_CHECK(hipEventRecord(ev[0], df.stream));
+      for (int r = 0; r < ranks; ++r) PE_HIP_CHECK(hipStreamWaitEvent(s[r]->stream(), ev[0], 0));
+    }
+    for (int r = 0; r < ranks; ++r) s[r]->enqueue_grad_stage();
+    exchange(0, false);
+    for (int r = 0; r < ranks; ++r) {
+      if (df.grad_x) s[r]->enqueue_grad(df.grad_x, df.grad_y, df.grad_si, df.grad_sj, blks[r].i0 - 1, blks[r].j0 - 1);
+      else if (gbuf) s[r]->enqueue_grad(gbuf, gbuf + gn, gny, 1, blks[r].i0 - 1, blks[r].j0 - 1);
+      else s[r]->enqueue_grad(nullptr, nullptr, 0, 0, 0, 0);
+    }
+    reduce(dg, 2, 0);
+    reduce(dg + ranks, 1, 1);
+    if (df.grad_x) {  // (reduce() joined every block's stream into s0)
+      PE_HIP_CHECK(hipEventRecord(ev[0], s0));
+      PE_HIP_CHECK(hipStreamWaitEvent(df.stream, ev[0], 0));
+    }
+    PE_HIP_CHECK(hipStreamSynchronize(s0));
+    PE_HIP_CHECK(hipFree(dg));
+  }
   for (int r = 0; r < ranks; ++r) s[r]->synchronize();
   s[0]->read_state(&hs);
+  if (gg.stats || grad_field) {
+    const double hh = P.h1() * P.h2();
+    res.grad.integral = hh * hs.res[0];
+    res.grad.energy = hh * hs.res[1];
+    res.grad.grad_max = std::sqrt(hs.res[2]);
+    if (gg.host) {
+      const size_t gn = size_t((int64_t(P.M) - 1) * (int64_t(P.N) - 1));
+      gg.host->resize(2 * gn);
+      PE_HIP_CHECK(hipMemcpy(gg.host->data(), gbuf, sizeof(double) * 2 * gn, hipMemcpyDeviceToHost));
+    }
+    if (gbuf) PE_HIP_CHECK(hipFree(gbuf));
+  }
   res.iters = hs.iter;
   res.converged = hs.status == 1;
   res.breakdown = hs.status == 2;

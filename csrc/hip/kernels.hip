@@ -660,6 +660,139 @@ __global__ __launch_bounds__(TJ) void kWtoP(KParams k, int b) {
   }
 }
 
+// Classic layout, before kGradField: owned w → the r plane, its first and last
+// columns → send_dn / send_up — what halo_plan() exchanges (kInit's stores).
+__global__ __launch_bounds__(TJ) void kWtoR(KParams k) {
+  const int64_t n = k.nx * k.ny;
+  for (int64_t idx = int64_t(blockIdx.x) * TJ + threadIdx.x; idx < n; idx += int64_t(gridDim.x) * TJ) {
+    const int64_t li = idx / k.ny + 1, lj = idx % k.ny + 1;
+    const double v = k.w[li * k.wpitch + lj];
+    k.r[li * k.pitch + lj] = v;
+    if (lj == 1 && k.has[DOWN]) k.send_dn[li - 1] = v;
+    if (lj == k.ny && k.has[UP]) k.send_up[li - 1] = v;
+  }
+}
+// … and after the exchange: recv_dn / recv_up → columns 0 / ny+1 of the r plane.
+__global__ __launch_bounds__(TJ) void kUnpackR(KParams k) {
+  for (int64_t li = int64_t(blockIdx.x) * TJ + threadIdx.x + 1; li <= k.nx; li += int64_t(gridDim.x) * TJ) {
+    if (k.has[DOWN]) k.r[li * k.pitch] = k.recv_dn[li - 1];
+    if (k.has[UP]) k.r[li * k.pitch + k.ny + 1] = k.recv_up[li - 1];
+  }
+}
+
+// Gradient of w and its functionals (pe/fields.hpp gradient_field, the same
+// expressions in the same order: the same bits).  `wp` is local (0, 0) of a
+// plane holding w on the owned nodes and the neighbours' values on the ring
+// (row stride `pitch`); ring values on the box boundary or outside the ellipse
+// are loaded but never used.  Work: tiles of kGradCols columns × `trows` rows,
+// tile t = (row band t / ctiles, column tile t % ctiles), dealt to the blocks
+// round-robin.  A block marches down its tile with one column per lane (sj == 1
+// stores coalesced), four rows per step: the rows above and below stay in
+// registers, the rows' left / right neighbours are re-read through the cache —
+// 8 B of w from memory and (STORE) 16 B written per node.  All indices 64-bit.
+// Sums: block partials → arrive_last → the last block sums them in block order
+// into st->res[0..2] = {Σ_D w, Σ_D (gx² + gy²), max_D (gx² + gy²)}.
+constexpr int kGradCols = TJ, kGradU = 4;
+__device__ __forceinline__ double grad_diff(bool in_lo, bool in_hi, double lo, double c, double hi, double h) {
+  // (operands selected first: one subtraction and one division whichever case)
+  const double a = in_hi ? hi : c, b = in_lo ? lo : c;
+  const double den = in_lo && in_hi ? 2.0 * h : h;
+  return in_lo || in_hi ? (a - b) / den : 0.0;
+}
+template <bool STORE>
+__global__ __launch_bounds__(TJ) void kGradField(KParams k, const double* __restrict__ wp, int64_t pitch, int trows,
+                                                 int64_t ctiles, int64_t ntiles, double* __restrict__ gx,
+                                                 double* __restrict__ gy, int64_t si, int64_t sj, int64_t off_i,
+                                                 int64_t off_j) {
+  __shared__ double sm[8];
+  __shared__ int sflag;
+  DevState* st = k.st;
+  double sw = 0.0, se = 0.0, mx = 0.0;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int64_t band = t / ctiles, ct = t - band * ctiles;
+    const int64_t lj0 = ct * kGradCols + threadIdx.x + 1;
+    const bool live = lj0 <= k.ny;
+    const int64_t lj = live ? lj0 : k.ny;  // (idle lanes of the last column tile load in range, store nothing)
+    const int64_t gj = k.gj0 + lj;
+    // cy·y² of columns j−1, j, j+1 (in_ellipse's own products); the box boundary is outside
+    const double ym = k.A2 + (gj - 1) * k.h2, y0 = k.A2 + gj * k.h2, yp = k.A2 + (gj + 1) * k.h2;
+    const double tym = k.cy * ym * ym, ty0 = k.cy * y0 * y0, typ = k.cy * yp * yp;
+    const bool jm_ok = gj - 1 >= 1, jp_ok = gj + 1 <= k.N - 1;
+    const int64_t li0 = band * trows + 1, li1 = min(k.nx, li0 + trows - 1);
+    const double* col = wp + lj;
+    double wm = col[(li0 - 1) * pitch], wc = col[li0 * pitch];
+    for (int64_t li = li0; li <= li1; li += kGradU) {
+      double dn[kGradU], dl[kGradU], dr[kGradU];
+#pragma unroll
+      for (int u = 0; u < kGradU; ++u) {  // (rows past the tile: clamped, loaded, unused)
+        const int64_t q = min(li + u, li1);
+        dn[u] = col[(q + 1) * pitch];
+        dl[u] = col[q * pitch - 1];
+        dr[u] = col[q * pitch + 1];
+      }
+#pragma unroll
+      for (int u = 0; u < kGradU; ++u) {
+        const int64_t q = li + u;
+        if (q <= li1) {
+          const int64_t gi = k.gi0 + q;
+          const double xm = k.A1 + (gi - 1) * k.h1, x0 = k.A1 + gi * k.h1, xp = k.A1 + (gi + 1) * k.h1;
+          const double txm = k.cx * xm * xm, tx0 = k.cx * x0 * x0, txp = k.cx * xp * xp;
+          const bool in0 = tx0 + ty0 < 1.0;
+          const bool in_im = gi - 1 >= 1 && txm + ty0 < 1.0, in_ip = gi + 1 <= k.M - 1 && txp + ty0 < 1.0;
+          const bool in_jm = jm_ok && tx0 + tym < 1.0, in_jp = jp_ok && tx0 + typ < 1.0;
+          double dx = 0.0, dy = 0.0;
+          if (in0) {
+            dx = grad_diff(in_im, in_ip, wm, wc, dn[u], k.h1);
+            dy = grad_diff(in_jm, in_jp, dl[u], wc, dr[u], k.h2);
+            if (live) {
+              const double g2 = dx * dx + dy * dy;
+              sw += wc;
+              se += g2;
+              mx = fmax(mx, g2);
+            }
+          }
+          if (STORE && live) {
+            const int64_t o = (off_i + q - 1) * si + (off_j + lj - 1) * sj;
+            gx[o] = dx;
+            gy[o] = dy;
+          }
+          wm = wc;
+          wc = dn[u];
+        }
+      }
+    }
+  }
+  double s[2] = {sw, se};
+  double m[1] = {mx};
+  block_reduce<2, false>(s, sm);
+  __syncthreads();
+  block_reduce<1, true>(m, sm);
+  if (threadIdx.x == 0) {
+    k.partial[3 * size_t(blockIdx.x)] = s[0];
+    k.partial[3 * size_t(blockIdx.x) + 1] = s[1];
+    k.partial[3 * size_t(blockIdx.x) + 2] = m[0];
+  }
+  if (arrive_last(&st->ticket[3], gridDim.x, &sflag)) {
+    double a0 = 0.0, a1 = 0.0, m0 = 0.0;
+    for (unsigned b = threadIdx.x; b < gridDim.x; b += TJ) {
+      a0 += k.partial[3 * size_t(b)];
+      a1 += k.partial[3 * size_t(b) + 1];
+      m0 = fmax(m0, k.partial[3 * size_t(b) + 2]);
+    }
+    double s2[2] = {a0, a1};
+    double mm[1] = {m0};
+    block_reduce<2, false>(s2, sm);
+    __syncthreads();
+    block_reduce<1, true>(mm, sm);
+    if (threadIdx.x == 0) {
+      st->res[0] = s2[0];
+      st->res[1] = s2[1];
+      st->res[2] = mm[0];
+      __hip_atomic_store(&st->ticket[3], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
 // p-plane of x[b] ← 0 over every allocated row and column (halos included):
 // rows 1-hdep .. nx+hdep+2, columns -xorg .. poff-xorg-1.
 __global__ __launch_bounds__(TJ) void kZeroP(KParams k, int b) {
@@ -836,6 +969,33 @@ void launch_resid(const KParams& k, int bw, bool with_r, bool store, hipStream_t
 }
 void launch_w_to_p(const KParams& k, int b, hipStream_t s) {
   hipLaunchKernelGGL(kWtoP, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, b);
+}
+void launch_w_to_r(const KParams& k, hipStream_t s) {
+  hipLaunchKernelGGL(kWtoR, dim3(flat_blocks(k)), dim3(TJ), 0, s, k);
+}
+void launch_unpack_r(const KParams& k, hipStream_t s) {
+  if (!k.has[DOWN] && !k.has[UP]) return;
+  const unsigned g = unsigned(std::max<int64_t>(1, std::min<int64_t>(1024, (k.nx + TJ - 1) / TJ)));
+  hipLaunchKernelGGL(kUnpackR, dim3(g), dim3(TJ), 0, s, k);
+}
+void launch_grad_field(const KParams& k, const double* plane, int64_t pitch, double* gx, double* gy, int64_t si,
+                       int64_t sj, int64_t off_i, int64_t off_j, hipStream_t s) {
+  // Rows per tile: enough tiles to fill the device (≈ 2048) where the block
+  // has them, between 8 rows (small blocks still make several tiles) and 64
+  // (the two ring rows a tile re-reads stay ≈ 3 % of its loads).  At most 4096
+  // blocks (k.partial holds 3 doubles for each); larger tile counts wrap.
+  const int64_t ctiles = (k.ny + kGradCols - 1) / kGradCols;
+  const int64_t bands = std::max<int64_t>(1, 2048 / ctiles);
+  const int trows = int(std::max<int64_t>(8, std::min<int64_t>(64, (k.nx + bands - 1) / bands)));
+  const int64_t ntiles = ctiles * ((k.nx + trows - 1) / trows);
+  const dim3 grid(unsigned(std::min<int64_t>(ntiles, 4096))), block(TJ);
+  if (gx && gy)
+    hipLaunchKernelGGL(kGradField<true>, grid, block, 0, s, k, plane, pitch, trows, ctiles, ntiles, gx, gy, si, sj,
+                       off_i, off_j);
+  else
+    hipLaunchKernelGGL(kGradField<false>, grid, block, 0, s, k, plane, pitch, trows, ctiles, ntiles,
+                       static_cast<double*>(nullptr), static_cast<double*>(nullptr), int64_t(0), int64_t(0), int64_t(0),
+                       int64_t(0));
 }
 void launch_zero_p(const KParams& k, int b, hipStream_t s) {
   hipLaunchKernelGGL(kZeroP, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, b);

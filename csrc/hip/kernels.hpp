@@ -72,6 +72,8 @@ struct DevState {
   // End-of-solve true-residual check (kResid): unweighted sums over the
   // owned nodes {Σρ², Σr², Σ(ρ − r)², ΣB²} of ρ = B − A w (the returned w)
   // and r the recurrence's residual of the same iterate (three-step).
+  // Once solve() has read them the slots (and ticket[3]) serve a gradient pass
+  // (kGradField): {Σ_D w, Σ_D (gx² + gy²), max_D (gx² + gy²)}.
   double res[4];
   // Three-step restart (residual replacement): β of iteration k0 + 1 is 0.
   long long k0;
@@ -317,6 +319,21 @@ void launch_error(const KParams& k, hipStream_t s, const double* exact = nullptr
 // from x[st->wpar] when with_r) → st->res; store: ρ → x[bw]'s r-plane.
 // rhs: the user right-hand side's device plane (dense nx × ny; null: F).
 void launch_resid(const KParams& k, int bw, bool with_r, bool store, hipStream_t s, const double* rhs = nullptr);
+// kGradField (pe/fields.hpp gradient_field's device twin): the gradient of w
+// on the owned nodes and its three functionals → st->res = {Σ_D w,
+// Σ_D (gx² + gy²), max_D (gx² + gy²)} (block partials summed in block order).
+// w is read with its one-node ring from `plane` (local (0, 0), row stride
+// `pitch`): the p-plane of x[0] after launch_w_to_p and the halo exchange, or
+// the classic r plane after launch_w_to_r / launch_unpack_r.  gx / gy (both or
+// neither; neither: the functionals only) are written as kGatherW writes w:
+// dst[(off_i + li) si + (off_j + lj) sj], li < nx, lj < ny.
+void launch_grad_field(const KParams& k, const double* plane, int64_t pitch, double* gx, double* gy, int64_t si,
+                       int64_t sj, int64_t off_i, int64_t off_j, hipStream_t s);
+// Classic layout, for kGradField: owned w → the r plane and its y strips →
+// send_dn / send_up (what halo_plan() exchanges); then recv_dn / recv_up →
+// columns 0 / ny+1 of the r plane.  Both clobber r: only a reset may follow.
+void launch_w_to_r(const KParams& k, hipStream_t s);
+void launch_unpack_r(const KParams& k, hipStream_t s);
 void launch_w_to_p(const KParams& k, int b, hipStream_t s);   // owned w → the p-plane of x[b]
 void launch_zero_p(const KParams& k, int b, hipStream_t s);   // the p-plane of x[b] ← 0 (halos included)
 void launch_restart3(const KParams& k, hipStream_t s);        // three-step restart state (kRestart3)

@@ -299,6 +299,30 @@ class DeviceSolver {
   // `consumer` (the destination may have work pending from its allocator's
   // stream), `consumer` waits for the gather.  Same pointer check as set_*_device.
   void copy_w_device(double* dst, int64_t si, int64_t sj, int64_t off_i, int64_t off_j, hipStream_t consumer);
+  // The gradient of w on the owned nodes and its functionals (pe/fields.hpp
+  // gradient_field; kGradField).  Valid after solve().  gradient(): gx / gy
+  // receive the owned nx × ny parts in host memory (both null: the
+  // functionals only, no field is written).  gradient_device(): gx / gy are
+  // float64 device memory of this solver's device, written like copy_w_device
+  // writes w — dst[(off_i + li) si + (off_j + lj) sj] — ordered with `consumer`
+  // by events only, after the same pointer check, before any launch (both
+  // null: the functionals only).  Collective on a multi-rank job (the halo of
+  // w is exchanged, the sums are reduced over ranks: every rank gets the
+  // job's figures).  Both use the iteration's own planes as scratch, as the
+  // end-of-solve residual pass does: afterwards only reset() or solve() may
+  // follow, and run_iterations() throws std::logic_error until then.
+  GradStats gradient(double* gx_host, double* gy_host);
+  GradStats gradient_device(double* gx, double* gy, int64_t si, int64_t sj, int64_t off_i, int64_t off_j,
+                            hipStream_t consumer);
+  // Its phases, for the virtual-rank group driver: w (flushed) → the plane the
+  // layout exchanges (+ its y strips); [the driver exchanges halo_phases(0)];
+  // the kernel (classic: its y strips unpacked first) → res_dev()[0..2].
+  void enqueue_grad_stage();
+  void enqueue_grad(double* gx, double* gy, int64_t si, int64_t sj, int64_t off_i, int64_t off_j);
+  double* res_dev();
+  // gradient_device()'s refusal: throws std::invalid_argument unless both destinations are device memory of this
+  // solver's device from element [0][0] to this block's last element
+  void check_grad_span(const double* gx, const double* gy, int64_t si, int64_t sj, int64_t off_i, int64_t off_j) const;
   // 0 r, 1 w, 2 p0, 3 p1 (single-sweep: 0 r of x[0], 2 p of x[0], 3 p of
   // x[1], 4 r of x[1]) as field_rows() × field_cols(), local (-h, -h) first.
   void copy_field(int which, double* host);
@@ -356,6 +380,8 @@ class DeviceSolver {
   // (with_r: against the recurrence's r; store: ρ → x[0]'s r-plane) and the
   // cross-rank sum of the four sums.
   void residual_pass(bool with_r, bool store);
+  // gradient() / gradient_device(): stage, halo exchange, kernel, cross-rank reductions, state read
+  GradStats gradient_pass(double* gx, double* gy, int64_t si, int64_t sj, int64_t off_i, int64_t off_j);
   void wait_event(hipEvent_t ev);  // event wait with transport-error polling + watchdog
   void enqueue_chunk(int iters, int sample_iters = 0);
   // Sampled phase timing (Timers): hipEvent pairs around the phases of the
@@ -420,6 +446,7 @@ class DeviceSolver {
   std::vector<std::pair<int, hipGraphExec_t>> graphs_;  // instantiated chunk graphs, by length
   int chunk_ = 16;
   int par_ = 0;  // parity of the next iteration (x / p ping-pong)
+  bool scratch_used_ = false;  // a gradient pass overwrote an iteration plane: reset() / solve() first
   double watchdog_s_ = 0;   // PE_WATCHDOG_S: abort if a chunk makes no progress this long (0 = off)
   bool fault_stall_ = false;  // PE_FAULT_INJECT=stall: pretend the device never finishes (watchdog test)
   // PE_FAULT_INJECT=drift@iter:K,amp:X — w(M/2, N/2) += X once the host has
@@ -507,12 +534,25 @@ struct DeviceFields {
   bool exact_f32 = false;
   double* w_dst = nullptr;    // (M-1) × (N-1), strides in elements
   int64_t w_si = 0, w_sj = 0;
-  hipStream_t stream = nullptr;  // the caller's stream (producer of the fields, consumer of w)
+  // destinations of the gradient (both or neither), (M-1) × (N-1) each with the same strides
+  double* grad_x = nullptr;
+  double* grad_y = nullptr;
+  int64_t grad_si = 0, grad_sj = 0;
+  hipStream_t stream = nullptr;  // the caller's stream (producer of the fields, consumer of w and the gradient)
+};
+// What the group driver computes of the gradient (DeviceSolver::gradient): nothing, the
+// functionals only (SolveResult::grad), or the field as well — into `host`
+// (gx then gy, 2 × (M-1)(N-1)) and / or DeviceFields::grad_x / grad_y, every
+// block writing its position; the sums go through the group reduction.
+struct GroupGradient {
+  bool stats = false;
+  std::vector<double>* host = nullptr;
 };
 SolveResult device_solve_group(const Problem& prob, int ranks, DecompMode mode, const SolveOptions& opt,
                                std::vector<double>* w_out = nullptr, const UserFields& fields = UserFields());
 SolveResult device_solve_group(const Problem& prob, const ProcessGrid& pg, const SolveOptions& opt,
                                std::vector<double>* w_out = nullptr, const UserFields& fields = UserFields(),
-                               const DeviceFields& dfields = DeviceFields());
+                               const DeviceFields& dfields = DeviceFields(),
+                               const GroupGradient& grad = GroupGradient());
 
 }  // namespace pe

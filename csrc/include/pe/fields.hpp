@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "pe/decomp.hpp"
+#include "pe/problem.hpp"
 
 namespace pe {
 
@@ -38,5 +39,27 @@ struct UserFields {
 // and zeros on the box boundary.  Local (li, lj) is global (i0-1+li, j0-1+lj)
 // as in Block; all indices 64-bit.
 std::vector<double> block_field(const double* g, int M, int N, const Block& blk, int ring);
+
+// The gradient of a solution and three integral functionals of it — one
+// definition for every backend (the device kernel kGradField is its twin).
+// in(i, j) = in_ellipse(x_i, y_j), false on the box boundary i ∈ {0, M},
+// j ∈ {0, N}.  At a node with in(i, j):
+//   gx = (w[i+1,j] − w[i−1,j]) / (2.0 h1)   both x neighbours inside,
+//        (w[i+1,j] − w[i,j]) / h1           only i+1 inside,
+//        (w[i,j] − w[i−1,j]) / h1           only i−1 inside,
+//        0.0                                neither;
+// gy alike in j with h2.  Outside the ellipse gx = gy = 0.0 whatever w is
+// there.  One subtraction and one true division per component: every backend
+// gives the same bits from the same w.
+//   integral = h1 h2 Σ_D w,  energy = h1 h2 Σ_D (gx² + gy²),
+//   grad_max = sqrt(max_D (gx² + gy²))   (the maximum is taken of the squares).
+// −1: not computed.
+struct GradStats {
+  double integral = -1.0, energy = -1.0, grad_max = -1.0;
+};
+
+// `w` is the global interior array of `prob`'s grid; gx / gy receive arrays of
+// the same shape (both null: the functionals only).  Host only.
+GradStats gradient_field(const Problem& prob, const double* w, double* gx, double* gy);
 
 }  // namespace pe

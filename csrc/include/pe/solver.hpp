@@ -112,6 +112,9 @@ struct SolveResult {
   // recurrence from w (residual replacement).
   double res_true = -1, res_rec = -1, res_gap = -1, b_norm = -1;
   int restarts = 0;
+  // The gradient's functionals (pe/fields.hpp), where the solve itself
+  // computes them (the virtual-rank group driver on request); -1 otherwise.
+  GradStats grad;
 };
 
 // ---- CPU backends (reference stage0..3 equivalents) -----------------------

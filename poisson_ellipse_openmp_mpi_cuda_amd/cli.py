@@ -25,6 +25,14 @@ is measured against inside the ellipse, e.g. a manufactured u with
 
     python -m poisson_ellipse_openmp_mpi_cuda_amd.cli --rhs f.npy --exact u.npy 400 600
 
+``--dump-grad FILE.npy`` writes the gradient of w inside the ellipse, float64
+of shape (2, M-1, N-1), [0] = d/dx, [1] = d/dy (one-sided differences at the
+boundary of the ellipse, 0 outside); ``--grad-stats`` prints h1 h2 Σ_D w,
+h1 h2 Σ_D |∇w|² and max_D |∇w| on a line of their own after the result lines
+(``--json`` carries them as ``integral``, ``energy``, ``grad_max``):
+
+    python -m poisson_ellipse_openmp_mpi_cuda_amd.cli --grad-stats --dump-grad g.npy 400 600
+
 Checkpoints hold the iteration state, not the fields: ``--resume`` needs the
 same ``--rhs`` (and ``--exact``) again, and ignores ``--w0``.
 """
@@ -85,6 +93,10 @@ def build_parser():
     ap.add_argument("--quiet", action="store_true", help="suppress the legacy lines")
     ap.add_argument("--dump", default=None, help="write w (interior) to this .npy")
     ap.add_argument("--pgm", default=None, help="write a grey-scale image of w")
+    ap.add_argument("--dump-grad", default=None, metavar="FILE.npy",
+                    help="write the gradient of w inside the ellipse, float64 (2, M-1, N-1): [0] d/dx, [1] d/dy")
+    ap.add_argument("--grad-stats", action="store_true",
+                    help="print h1 h2 sum_D w, h1 h2 sum_D |grad w|^2 and max_D |grad w| after the result lines")
     return ap
 
 
@@ -107,7 +119,8 @@ def main(argv=None) -> int:
     rep = solve(prob, backend=a.backend, ranks=a.ranks, threads=a.threads, decomp=a.decomp, init=a.init,
                 seed=a.seed, return_w=want_w, variant=a.variant, timing=a.timing, graph=a.graph and not a.no_graph,
                 algo=a.algo, checkpoint=a.checkpoint, checkpoint_every=a.checkpoint_every, resume=a.resume,
-                log_every=a.log_every, rhs=rhs, w0=w0, exact=exact)
+                log_every=a.log_every, rhs=rhs, w0=w0, exact=exact,
+                return_grad=True if a.dump_grad else "stats" if a.grad_stats else False)
     if rep.rank != 0:
         return 0
     if not a.quiet:
@@ -117,8 +130,13 @@ def main(argv=None) -> int:
         else:
             err = "L2 error in D ~ n/a (user right-hand side)"
         print(f"   Process grid {rep.Px}x{rep.Py} | iters/s ~ {rep.iters_per_s:.1f} | {err}")
+    if a.grad_stats:
+        print(f"   Integral of w in D ~ {rep.integral:.6e} | energy ~ {rep.energy:.6e} | max |grad w| in D ~ "
+              f"{rep.grad_max:.6e}")
     if a.json:
         print(json_report(rep))
+    if a.dump_grad and rep.grad is not None:
+        np.save(a.dump_grad, rep.grad)
     if want_w and rep.w is not None:
         if a.dump:
             _dump.save(a.dump, rep.w, prob, rep)

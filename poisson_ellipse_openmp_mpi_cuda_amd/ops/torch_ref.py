@@ -446,6 +446,35 @@ def three_step(prob: EllipseProblem, sweeps: int, device="cpu", *, rhs=None, w0=
     return ThreeStepState(sweeps, sums, alphas, betas, diffs, r, p, w)
 
 
+def gradient(prob: EllipseProblem, W: torch.Tensor):
+    """The gradient of a solution and its functionals, the definition of
+    pe::gradient_field (csrc/include/pe/fields.hpp) in torch: W is the full
+    (M+1, N+1) tensor (pcg's ``w``).  Returns (g, integral, energy, grad_max),
+    g of shape (2, M-1, N-1) over the interior, [0] = ∂x, [1] = ∂y: central
+    differences where both neighbours are inside the ellipse, one-sided where
+    one is, 0 where neither is and at every node outside; one subtraction and
+    one true division per component (tensor / tensor), the bits of the other
+    backends from the same w."""
+    x, y = _grid(prob, W.device)
+    X, Y = x[:, None], y[None, :]
+    inside = (prob.cx * X * X + prob.cy * Y * Y) < 1.0
+    inside[0, :] = inside[-1, :] = False
+    inside[:, 0] = inside[:, -1] = False
+    c, in0 = W[1:-1, 1:-1], inside[1:-1, 1:-1]
+
+    def diff(lo, hi, in_lo, in_hi, h):
+        num = torch.where(in_hi, hi, c) - torch.where(in_lo, lo, c)
+        den = torch.where(in_lo & in_hi, torch.full_like(c, 2.0 * h), torch.full_like(c, h))
+        return torch.where(in0 & (in_lo | in_hi), num / den, torch.zeros_like(c))
+
+    gx = diff(W[:-2, 1:-1], W[2:, 1:-1], inside[:-2, 1:-1], inside[2:, 1:-1], prob.h1)
+    gy = diff(W[1:-1, :-2], W[1:-1, 2:], inside[1:-1, :-2], inside[1:-1, 2:], prob.h2)
+    g2 = gx * gx + gy * gy
+    hh = prob.h1 * prob.h2
+    integral = hh * float(torch.where(in0, c, torch.zeros_like(c)).sum())
+    return torch.stack((gx, gy)), integral, hh * float(g2.sum()), math.sqrt(float(g2.max()))
+
+
 def error_vs_analytic(prob: EllipseProblem, w: torch.Tensor, u: Optional[torch.Tensor] = None):
     """(L2 error in D, h-weighted; max error in D) against u = F(1-cx x²-cy y²)/(2cx+2cy),
     or against a given u of w's shape (a user exact solution, embedded)."""

@@ -84,6 +84,13 @@ class SolveReport:
     # return_w="device" on a multi-process hip job: w is this rank's owned block and (i0, j0) the global
     # 1-based node index of its first entry (None: w is the global array)
     w_origin: Optional[tuple] = None
+    # return_grad: the gradient of w, float64 (2, M-1, N-1), [0] = d/dx, [1] = d/dy (True: numpy; "device": a GPU
+    # tensor written by the solver, on a multi-process job this rank's block (2, nx, ny) at w_origin), and its
+    # functionals h1 h2 sum_D w, h1 h2 sum_D |grad|^2 and max_D |grad| (-1: not requested)
+    grad: Optional[np.ndarray] = None
+    integral: float = -1.0
+    energy: float = -1.0
+    grad_max: float = -1.0
 
     @property
     def iters_per_s(self) -> float:
@@ -91,8 +98,10 @@ class SolveReport:
         return self.iters / t if t > 0 else 0.0
 
     def to_dict(self) -> dict:
-        d = dataclasses.asdict(dataclasses.replace(self, w=None))  # (w, array or device tensor, is not copied)
+        # (w and grad, arrays or device tensors, are not copied)
+        d = dataclasses.asdict(dataclasses.replace(self, w=None, grad=None))
         d.pop("w", None)
+        d.pop("grad", None)
         d["iters_per_s"] = self.iters_per_s
         return d
 
@@ -212,9 +221,32 @@ def _report(backend, prob, res, ranks, threads, init, w=None, rank=0) -> SolveRe
         b_norm=float(getattr(res, "b_norm", -1.0)), restarts=int(getattr(res, "restarts", 0)))
 
 
+def _grad_mode(return_grad, on_device: bool, backend: str = "hip"):
+    """return_grad as solve() takes it → False, "stats", True or "device"; ValueError otherwise."""
+    if isinstance(return_grad, str):
+        if return_grad not in ("stats", "device"):
+            raise ValueError('return_grad must be True, False, "stats" or "device"')
+        if return_grad == "device" and not on_device:
+            raise ValueError(f'return_grad="device" needs backend "hip" or "hip-group", not "{backend}"')
+        return return_grad
+    return bool(return_grad)
+
+
+def _set_grad(rep: SolveReport, stats, g=None) -> SolveReport:
+    rep.integral, rep.energy, rep.grad_max = (float(v) for v in stats)
+    rep.grad = g
+    return rep
+
+
+def _host_gradient(rep: SolveReport, prob: EllipseProblem, w, mode) -> SolveReport:
+    """The gradient of the gathered w on the host (native.gradient_field): the CPU backends."""
+    stats, g = native().gradient_field(prob.to_native(), w, mode is True)
+    return _set_grad(rep, stats, None if g is None else np.asarray(g))
+
+
 def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: int = 1, decomp: str | None = None,
           init: str = "zero", seed: int = 1234, return_w: bool | str = False, device: str = "cuda", rhs=None,
-          w0=None, exact=None, **kw) -> SolveReport:
+          w0=None, exact=None, return_grad: bool | str = False, **kw) -> SolveReport:
     """Solve the fictitious-domain Poisson problem with the chosen backend.
 
     ``rhs`` / ``w0`` (every backend): a user right-hand side and initial guess
@@ -252,6 +284,19 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
     first entry (no gather).  DeviceSession keeps one constructed solver for a
     sequence of such solves.
 
+    ``return_grad`` (every backend): the gradient of the returned ``w`` inside
+    the ellipse and three functionals of it, from one definition
+    (csrc/include/pe/fields.hpp): central differences where both neighbours
+    are inside the ellipse, one-sided where one is (``w`` drops to O(ε)
+    across the fictitious-domain boundary), 0 outside.  ``"stats"`` fills
+    ``integral`` = h1·h2·Σ_D w, ``energy`` = h1·h2·Σ_D |∇w|² and ``grad_max``
+    = max_D |∇w|; ``True`` also returns ``grad``, float64 (2, M-1, N-1),
+    [0] = ∂x, [1] = ∂y (gathered onto rank 0 on a multi-process job, as w
+    is); ``"device"`` (``hip`` / ``hip-group``) returns it as a GPU tensor
+    written by the solver — on a multi-process job this rank's block
+    (2, nx, ny) at ``w_origin``.  Every backend gives the same bits from the
+    same ``w``.  The solve itself is that of the same call without it.
+
     For ``hip`` with torch.distributed initialised and world > 1 this is the
     per-rank call of a multi-GPU job (every rank calls it; rank 0's report
     carries the max-over-ranks timers and, with return_w, the gathered w).
@@ -259,6 +304,7 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
     if backend not in BACKENDS:
         raise ValueError(f"backend must be one of {BACKENDS}")
     on_device = backend in ("hip", "hip-group")
+    grad = _grad_mode(return_grad, on_device, backend)
     if isinstance(return_w, str):
         if return_w != "device":
             raise ValueError('return_w must be True, False or "device"')
@@ -277,8 +323,9 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
         nranks = ranks if backend == "ranks" else 1
         opt = _options(init, seed, t, keep_history=kw.get("keep_history", False), log_every=kw.get("log_every", 0))
         res, w = nat.cpu_solve_grid(P, _decomp.grid(nranks, prob.M, prob.N, decomp if backend == "ranks" else "reference"),
-                                    opt, return_w, rhs, w0, exact)
-        return _report(backend, prob, res, nranks, t, init, None if w is None else np.asarray(w))
+                                    opt, bool(return_w or grad), rhs, w0, exact)
+        rep = _report(backend, prob, res, nranks, t, init, np.asarray(w) if return_w else None)
+        return _host_gradient(rep, prob, w, grad) if grad else rep
     if backend == "torch":
         import torch
 
@@ -291,16 +338,21 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
                           exact=exact)
         dt = time.perf_counter() - t0
         timers = dict(solver=dt, iterate=dt)
-        return SolveReport("torch", prob.M, prob.N, 1, 1, 1, 1, r.iters, r.converged, False,
-                           r.history[-1] if r.history else 0.0, timers, r.l2_err, r.max_err, -1.0,
-                           "zero" if w0 is None else "field",
-                           r.w[1:-1, 1:-1].cpu().numpy() if return_w else None)
+        rep = SolveReport("torch", prob.M, prob.N, 1, 1, 1, 1, r.iters, r.converged, False,
+                          r.history[-1] if r.history else 0.0, timers, r.l2_err, r.max_err, -1.0,
+                          "zero" if w0 is None else "field",
+                          r.w[1:-1, 1:-1].cpu().numpy() if return_w else None)
+        if grad:
+            g, *stats = torch_ref.gradient(prob, r.w)
+            _set_grad(rep, stats, g.cpu().numpy() if grad is True else None)
+        return rep
     if backend == "hip-group":
         opt = _options(init, seed, chunk=kw.get("chunk", 0), timing=kw.get("timing", False),
                        variant=kw.get("variant", 0), check_tol=kw.get("check_tol", True),
                        algo=kw.get("algo", "auto"))
         pg = _decomp.grid(ranks, prob.M, prob.N, decomp)
-        if not (is_device_tensor(rhs) or is_device_tensor(w0) or is_device_tensor(exact) or return_w == "device"):
+        if not (is_device_tensor(rhs) or is_device_tensor(w0) or is_device_tensor(exact) or return_w == "device"
+                or grad):
             res, w = nat.device_solve_group_grid(P, pg, opt, return_w, rhs, w0, exact)
             return _report(backend, prob, res, ranks, 1, init, None if w is None else np.asarray(w))
         import torch
@@ -313,12 +365,25 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
         if return_w == "device":  # every block gathers into its position of this one tensor
             wt = torch.empty((prob.M - 1, prob.N - 1), dtype=torch.float64, device=f"cuda:{index}")
             w_dev = (wt.data_ptr(), wt.stride(0), wt.stride(1))
-        res, w = nat.device_solve_group_grid_device(P, pg, opt, bool(return_w) and wt is None, host.get("rhs"),
-                                                    host.get("w0"), dev.get("rhs"), dev.get("w0"), w_dev,
-                                                    _stream_handle(index), host.get("exact"), dev.get("exact"))
+        if not grad:
+            res, w = nat.device_solve_group_grid_device(P, pg, opt, bool(return_w) and wt is None, host.get("rhs"),
+                                                        host.get("w0"), dev.get("rhs"), dev.get("w0"), w_dev,
+                                                        _stream_handle(index), host.get("exact"), dev.get("exact"))
+            if wt is None and w is not None:
+                wt = np.asarray(w)
+            return _report(backend, prob, res, ranks, 1, init, wt)
+        gt = g_dev = None
+        if grad == "device":  # every block's kernel writes its position of this one tensor
+            gt = torch.empty((2, prob.M - 1, prob.N - 1), dtype=torch.float64, device=f"cuda:{index}")
+            g_dev = (gt[0].data_ptr(), gt[1].data_ptr(), gt.stride(1), gt.stride(2))
+        res, w, g = nat.device_solve_group_grad(P, pg, opt, bool(return_w) and wt is None, 1 if grad == "stats" else 2,
+                                                host.get("rhs"), host.get("w0"), host.get("exact"), dev.get("rhs"),
+                                                dev.get("w0"), dev.get("exact"), w_dev, g_dev, _stream_handle(index))
         if wt is None and w is not None:
             wt = np.asarray(w)
-        return _report(backend, prob, res, ranks, 1, init, wt)
+        if gt is None and g is not None:
+            gt = np.asarray(g)
+        return _set_grad(_report(backend, prob, res, ranks, 1, init, wt), res.grad, gt)
     # distributed backends
     from .parallel import dist as _dist
 
@@ -327,11 +392,13 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
         blk = _decomp.block(prob.M, prob.N, ctx.world, ctx.rank, decomp)
         opt = _options(init, seed, max(1, threads))
         res, w = nat.cpu_solve_rank(P, blk, *_dist.gloo_callbacks(), opt, True, rhs, w0, exact)
-        wg = _dist.gather_blocks(ctx, prob, blk, np.asarray(w)) if return_w else None
-        return _report(backend, prob, res, ctx.world, threads, init, wg, ctx.rank)
+        wg = _dist.gather_blocks(ctx, prob, blk, np.asarray(w)) if return_w or grad else None
+        rep = _report(backend, prob, res, ctx.world, threads, init, wg if return_w else None, ctx.rank)
+        # (the gathered w lives on rank 0: its report carries the gradient and the figures)
+        return _host_gradient(rep, prob, wg, grad) if grad and wg is not None else rep
     # hip
     with DeviceSession(prob, decomp, init=init, seed=seed, **kw) as session:
-        return session._solve(rhs, w0, return_w, exact)
+        return session._solve(rhs, w0, return_w, exact, grad)
 
 
 _HIP_OPTIONS = ("chunk", "graph", "timing", "check_tol", "variant", "algo", "checkpoint_every", "checkpoint", "resume",
@@ -393,17 +460,19 @@ class DeviceSession:
         self.close()
         return False
 
-    def solve(self, rhs=None, w0=None, exact=None, return_w=False) -> SolveReport:
+    def solve(self, rhs=None, w0=None, exact=None, return_w=False, return_grad=False) -> SolveReport:
         """One solve on the kept solver.  ``rhs`` / ``w0`` / ``exact``: host
         arrays or GPU tensors of the global interior, per call and mixed
         freely; None clears a field back to F / ``init`` / the analytic error.  ``return_w``: False, True (numpy; on a
         multi-process job gathered onto rank 0) or "device" (a float64 GPU
         tensor written by the solver; on a multi-process job this rank's block,
-        its position in the report's ``w_origin``)."""
+        its position in the report's ``w_origin``).  ``return_grad``: False,
+        "stats", True or "device", as in solve()."""
         if isinstance(return_w, str) and return_w != "device":
             raise ValueError('return_w must be True, False or "device"')
+        grad = _grad_mode(return_grad, True)
         return self._solve(_field_arg("rhs", rhs, self.prob, True), _field_arg("w0", w0, self.prob, True), return_w,
-                           _field_arg("exact", exact, self.prob, True))
+                           _field_arg("exact", exact, self.prob, True), grad)
 
     def _set_fields(self, rhs, w0, exact=None) -> None:
         """The three fields into the solver's planes; everything is checked
@@ -422,7 +491,32 @@ class DeviceSession:
             else:
                 set_host(local)  # (None clears)
 
-    def _solve(self, rhs, w0, return_w, exact=None) -> SolveReport:
+    def _gradient(self, rep: SolveReport, grad) -> None:
+        """The gradient pass of the kept solver after its solve (collective on a
+        multi-process job) into the report; `grad`: "stats", True or "device"."""
+        from .parallel import dist as _dist
+
+        s, blk = self.solver, self.block
+        if grad == "device":
+            import torch
+
+            # single process: the block is the global interior; otherwise this rank's owned block
+            g = torch.empty((2, blk.nx, blk.ny), dtype=torch.float64, device=f"cuda:{self.device_index}")
+            stats = s.gradient_device(g[0].data_ptr(), g[1].data_ptr(), g.stride(1), g.stride(2), 0, 0,
+                                      _stream_handle(self.device_index))
+            if self.world > 1:
+                rep.w_origin = (int(blk.i0), int(blk.j0))
+        else:
+            stats, gx, gy = s.gradient(grad is True)
+            g = None
+            if grad is True and self.world == 1:
+                g = np.stack((np.asarray(gx), np.asarray(gy)))
+            elif grad is True:
+                parts = [_dist.gather_blocks(_dist.init(), self.prob, blk, np.asarray(c)) for c in (gx, gy)]
+                g = None if parts[0] is None else np.stack(parts)
+        _set_grad(rep, stats, g)
+
+    def _solve(self, rhs, w0, return_w, exact=None, grad=False) -> SolveReport:
         # rhs / w0 / exact: None, checked host arrays or GPU tensors of checked shape and dtype (_field_arg)
         from .parallel import dist as _dist
 
@@ -452,6 +546,14 @@ class DeviceSession:
             w = wl if self.world == 1 else _dist.gather_blocks(_dist.init(), prob, self.block, wl)
         rep = _report("hip", prob, res, self.world, 1, "field" if w0 is not None else self.init, w, self.rank)
         rep.w_origin = origin
+        # (a multi-process solve that ended non-finite has dropped its communicator: no collective pass after it)
+        if grad and (comm is None or (np.isfinite(res.last_diff) and not res.nonfinite)):
+            try:
+                self._gradient(rep, grad)
+            except Exception:
+                if comm is not None:
+                    _dist.drop_comm(comm)
+                raise
         rep.comm = comm.name if comm is not None else "self"
         rep.xr = bool(s.xr)
         rep.halo_push = bool(s.halo_push)
