@@ -1,9 +1,9 @@
 // pe_fields: cuts every block's share out of a global interior array whose
 // value encodes (i, j) and checks it node by node — the owned parts tile the
 // interior, the rings hold the neighbours' values and zeros on the box
-// boundary.  Then pe::gradient_field on two small grids against the
-// definition written out.  No device: the sanitizer build's driver of
-// pe/fields.hpp (make asan).
+// boundary.  Then pe::gradient_field, pe::apply_operator and
+// pe::residual_field on two small grids against their definitions written
+// out.  No device: the sanitizer build's driver of pe/fields.hpp (make asan).
 //   pe_fields M N PX PY
 #include <algorithm>
 #include <cmath>
@@ -58,6 +58,56 @@ static int64_t check_gradient(const pe::Problem& P) {
   return bad;
 }
 
+// Mismatches of pe::apply_operator / pe::residual_field on P's grid against a
+// naive double loop over full coefficient arrays and a zero-padded copy of a
+// field that is non-zero everywhere; one and three threads, with and without
+// a destination, built-in F and a user right-hand side.
+static int64_t check_operator(const pe::Problem& P) {
+  const int64_t M = P.M, N = P.N, gny = N - 1, n = (M - 1) * gny, C = N + 2;
+  const double h1 = P.h1(), h2 = P.h2(), eps = P.eps();
+  std::vector<double> v(static_cast<size_t>(n)), f(v.size());
+  std::vector<double> V(size_t((M + 2) * C), 0.0), a(V.size(), 0.0), b(V.size(), 0.0);
+  for (int64_t i = 0; i <= M; ++i)
+    for (int64_t j = 0; j <= N; ++j) {
+      const double x = P.A1 + i * h1, y = P.A2 + j * h2;
+      a[size_t(i * C + j)] = pe::face_coef(pe::seg_len_vertical(x - 0.5 * h1, y - 0.5 * h2, y + 0.5 * h2, P.cx, P.cy, P.sx), h2, eps);
+      b[size_t(i * C + j)] = pe::face_coef(pe::seg_len_horizontal(y - 0.5 * h2, x - 0.5 * h1, x + 0.5 * h1, P.cx, P.cy, P.sy), h1, eps);
+      if (i >= 1 && i < M && j >= 1 && j < N) {
+        const double val = 0.25 + 0.01 * double((i * 37 + j * 11) % 29) - 0.003 * double(j);
+        v[size_t((i - 1) * gny + (j - 1))] = val;
+        V[size_t(i * C + j)] = val;
+        f[size_t((i - 1) * gny + (j - 1))] = 1.0 + 0.1 * double((i * 5 + j * 3) % 7);
+      }
+    }
+  int64_t bad = 0;
+  for (int mode = 0; mode < 3; ++mode) {  // 0: A v; 1: F − A v; 2: f − A v
+    const double* rhs = mode == 2 ? f.data() : nullptr;
+    std::vector<double> want(v.size());
+    double s = 0.0;
+    for (int64_t i = 1; i < M; ++i)
+      for (int64_t j = 1; j < N; ++j) {
+        const int64_t c = i * C + j, o = (i - 1) * gny + (j - 1);
+        const double Ax = -1.0 / h1 * (a[size_t(c + C)] * (V[size_t(c + C)] - V[size_t(c)]) / h1 - a[size_t(c)] * (V[size_t(c)] - V[size_t(c - C)]) / h1);
+        const double Ay = -1.0 / h2 * (b[size_t(c + 1)] * (V[size_t(c + 1)] - V[size_t(c)]) / h2 - b[size_t(c)] * (V[size_t(c)] - V[size_t(c - 1)]) / h2);
+        double r = Ax + Ay;
+        if (mode) {
+          const bool in = pe::in_ellipse(P.A1 + i * h1, P.A2 + j * h2, P.cx, P.cy);
+          r = (in ? (rhs ? rhs[size_t(o)] : P.F) : 0.0) - r;
+        }
+        want[size_t(o)] = r;
+        s += mode ? r * r : V[size_t(c)] * r;
+      }
+    for (int T : {1, 3}) {
+      std::vector<double> got(v.size(), -7.0);
+      const double sum = mode ? pe::residual_field(P, v.data(), rhs, got.data(), T) : pe::apply_operator(P, v.data(), got.data(), T);
+      const double only = mode ? pe::residual_field(P, v.data(), rhs, nullptr, T) : pe::apply_operator(P, v.data(), nullptr, T);
+      if (got != want || only != sum) ++bad;
+      if (T == 1 ? sum != h1 * h2 * s : std::fabs(sum - h1 * h2 * s) > 1e-12 * std::fabs(h1 * h2 * s)) ++bad;
+    }
+  }
+  return bad;
+}
+
 int main(int argc, char** argv) {
   if (argc != 5) {
     std::fprintf(stderr, "usage: pe_fields M N PX PY\n");
@@ -107,5 +157,7 @@ int main(int argc, char** argv) {
   tiny.sx = tiny.sy = std::sqrt(30.0);
   const int64_t gbad = check_gradient(ref) + check_gradient(tiny);
   std::printf("pe_fields gradient_field 10x50, 12x12 (cx = cy = 30): %s\n", gbad ? "MISMATCH" : "ok");
-  return bad || gbad ? 1 : 0;
+  const int64_t obad = check_operator(ref) + check_operator(tiny);
+  std::printf("pe_fields apply_operator / residual_field 10x50, 12x12 (cx = cy = 30): %s\n", obad ? "MISMATCH" : "ok");
+  return bad || gbad || obad ? 1 : 0;
 }

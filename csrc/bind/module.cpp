@@ -369,6 +369,46 @@ PYBIND11_MODULE(_native, m) {
       },
       py::arg("prob"), py::arg("w"), py::arg("field") = true);
 
+  // The operator applied to a global interior array, and the residual field
+  // B − A w (pe/fields.hpp apply_operator / residual_field): (sum, field) with
+  // the field of shape (M-1, N-1) — or None with field=False.  sum =
+  // h1·h2·Σ v·(A v), or h1·h2·Σ (B − A w)².
+  m.def(
+      "apply_operator",
+      [](const Problem& P, py::object v, bool field, int threads) {
+        FieldArr h;
+        const double* p = field_ptr(v, int64_t(P.M) - 1, int64_t(P.N) - 1, "v", h);
+        if (!p) throw std::invalid_argument("apply_operator: the array is None");
+        std::vector<double> out(field ? size_t((int64_t(P.M) - 1) * (int64_t(P.N) - 1)) : 0);
+        double sum;
+        {
+          py::gil_scoped_release nogil;
+          sum = apply_operator(P, p, field ? out.data() : nullptr, threads);
+        }
+        py::object oa = py::none();
+        if (field) oa = to_array(std::move(out), P.M - 1, P.N - 1);
+        return py::make_tuple(sum, oa);
+      },
+      py::arg("prob"), py::arg("v"), py::arg("field") = true, py::arg("threads") = 1);
+  m.def(
+      "residual_field",
+      [](const Problem& P, py::object w, py::object rhs, bool field, int threads) {
+        FieldArr h, hr;
+        const double* p = field_ptr(w, int64_t(P.M) - 1, int64_t(P.N) - 1, "w", h);
+        if (!p) throw std::invalid_argument("residual_field: the array is None");
+        const double* r = field_ptr(rhs, int64_t(P.M) - 1, int64_t(P.N) - 1, "rhs", hr);
+        std::vector<double> out(field ? size_t((int64_t(P.M) - 1) * (int64_t(P.N) - 1)) : 0);
+        double sum;
+        {
+          py::gil_scoped_release nogil;
+          sum = residual_field(P, p, r, field ? out.data() : nullptr, threads);
+        }
+        py::object oa = py::none();
+        if (field) oa = to_array(std::move(out), P.M - 1, P.N - 1);
+        return py::make_tuple(sum, oa);
+      },
+      py::arg("prob"), py::arg("w"), py::arg("rhs") = py::none(), py::arg("field") = true, py::arg("threads") = 1);
+
   m.def("host_coefficients", [](const Problem& P, const Block& blk) {
     std::vector<double> a, b;
     std::vector<int> c;
@@ -669,6 +709,44 @@ PYBIND11_MODULE(_native, m) {
           "the same with gx / gy written into float64 device memory at element offset (off_i, off_j), ordered with "
           "`stream` (both addresses 0: the functionals only); returns (integral, energy, grad_max)")
       .def(
+          "apply",
+          [](DeviceSolver& s, py::object v, bool resid, bool field) {
+            FieldArr h;
+            const double* p = field_ptr(v, int64_t(s.problem().M) - 1, int64_t(s.problem().N) - 1, "field", h);
+            if (!p) throw std::invalid_argument("apply: the array is None");
+            const Block& b = s.block();
+            std::vector<double> out(field ? size_t(b.nx * b.ny) : 0);
+            double sum;
+            {
+              py::gil_scoped_release nogil;
+              sum = resid ? s.residual(p, field ? out.data() : nullptr) : s.apply(p, field ? out.data() : nullptr);
+            }
+            py::object oa = py::none();
+            if (field) oa = to_array(std::move(out), b.nx, b.ny);
+            return py::make_tuple(sum, oa);
+          },
+          py::arg("v"), py::arg("residual") = false, py::arg("field") = true,
+          "(sum, field) of A v — or (residual) of B − A v, B the rhs that is set, else F — for the GLOBAL (M-1) × "
+          "(N-1) host array v: the field on this block's owned nodes (field=False: None), sum = the job's h1 h2 Σ "
+          "v·(A v) or h1 h2 Σ (B − A v)²; collective on a multi-rank job; disturbs no state of the solve")
+      .def(
+          "apply_device",
+          [](DeviceSolver& s, uintptr_t ptr, int64_t si, int64_t sj, bool f32, bool resid, uintptr_t dst, int64_t dsi,
+             int64_t dsj, int64_t off_i, int64_t off_j, uintptr_t stream) {
+            py::gil_scoped_release nogil;
+            const void* v = reinterpret_cast<const void*>(ptr);
+            double* d = reinterpret_cast<double*>(dst);
+            hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+            return resid ? s.residual_device(v, si, sj, f32, d, dsi, dsj, off_i, off_j, st)
+                         : s.apply_device(v, si, sj, f32, d, dsi, dsj, off_i, off_j, st);
+          },
+          py::arg("ptr"), py::arg("stride_i"), py::arg("stride_j"), py::arg("f32") = false, py::arg("residual") = false,
+          py::arg("dst") = 0, py::arg("dst_stride_i") = 0, py::arg("dst_stride_j") = 0, py::arg("off_i") = 0,
+          py::arg("off_j") = 0, py::arg("stream") = 0,
+          "the same with the GLOBAL array in device memory (address of element [0][0], element strides, float32 "
+          "flag) and the owned part written into float64 device memory at element offset (off_i, off_j) of `dst` "
+          "(0: the sum only), ordered with `stream`; returns the sum")
+      .def(
           "user_plane",
           [](DeviceSolver& s, int which) -> py::object {
             std::vector<double> v = s.user_plane(which);
@@ -939,6 +1017,42 @@ PYBIND11_MODULE(_native, m) {
       py::arg("w0") = py::none(), py::arg("exact") = py::none(), py::arg("rhs_dev") = py::none(),
       py::arg("w0_dev") = py::none(), py::arg("exact_dev") = py::none(), py::arg("w_dev") = py::none(),
       py::arg("grad_dev") = py::none(), py::arg("stream") = 0);
+
+  // The operator (residual: B − A w) on P virtual ranks of one device: v / rhs
+  // as host arrays or device specs (address, stride_i, stride_j, float32
+  // flag); out_dev = (address, stride_i, stride_j) of a float64 (M-1) × (N-1)
+  // destination, else field=True returns the array.  Returns (sum, field).
+  m.def(
+      "device_apply_group",
+      [](const Problem& P, const ProcessGrid& pg, const SolveOptions& opt, bool residual, py::object v, py::object v_dev,
+         py::object rhs, py::object rhs_dev, py::object out_dev, bool field, uintptr_t stream) {
+        FieldArr hv, hr;
+        OperatorFields f;
+        f.v_host = field_ptr(v, P.M - 1, P.N - 1, "field", hv);
+        f.rhs_host = field_ptr(rhs, P.M - 1, P.N - 1, "rhs", hr);
+        device_spec(v_dev, f.v, f.v_si, f.v_sj, f.v_f32);
+        device_spec(rhs_dev, f.rhs, f.rhs_si, f.rhs_sj, f.rhs_f32);
+        f.stream = reinterpret_cast<hipStream_t>(stream);
+        if (!out_dev.is_none()) {
+          const auto t = out_dev.cast<std::tuple<uintptr_t, int64_t, int64_t>>();
+          f.dst = reinterpret_cast<double*>(std::get<0>(t));
+          f.dst_si = std::get<1>(t);
+          f.dst_sj = std::get<2>(t);
+        }
+        std::vector<double> out;
+        if (field && out_dev.is_none()) f.host = &out;
+        double sum;
+        {
+          py::gil_scoped_release nogil;
+          sum = device_apply_group(P, pg, opt, f, residual);
+        }
+        py::object oa = py::none();
+        if (f.host) oa = to_array(std::move(out), P.M - 1, P.N - 1);
+        return py::make_tuple(sum, oa);
+      },
+      py::arg("prob"), py::arg("grid"), py::arg("opt"), py::arg("residual") = false, py::arg("v") = py::none(),
+      py::arg("v_dev") = py::none(), py::arg("rhs") = py::none(), py::arg("rhs_dev") = py::none(),
+      py::arg("out_dev") = py::none(), py::arg("field") = true, py::arg("stream") = 0);
 
   // Single-shot device ops for numerics tests: `p` is a full local field
   // (rows × pitch, halo included); returns arrays of the same shape.

@@ -1,9 +1,12 @@
 // Slicing of global interior arrays (user right-hand side / initial guess)
-// into one block's share, and the gradient of a global solution array.  Host only.
+// into one block's share, the gradient of a global solution array, and the
+// operator / residual of a global field.  Host only.
 #include "pe/fields.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <stdexcept>
+#include <string>
 
 namespace pe {
 
@@ -69,6 +72,82 @@ GradStats gradient_field(const Problem& P, const double* w, double* gx, double* 
   s.energy = h1 * h2 * se;
   s.grad_max = std::sqrt(mx);
   return s;
+}
+
+namespace {
+
+// Rows lo .. hi (global node rows, 1-based) of out = A v, or (resid) of
+// out = B − A v; returns this range's Σ v·(A v) or Σ out², row-major.  The
+// coefficient rows a_i, a_{i+1} (vertical faces left of the nodes of rows i,
+// i+1) and b_i (horizontal faces below the nodes of row i, columns 1 .. N)
+// are formed row by row with assemble()'s expressions.
+double operator_rows(const Problem& P, const double* v, bool resid, const double* rhs, double* out, int64_t lo,
+                     int64_t hi) {
+  const int64_t M = P.M, N = P.N, gny = N - 1;
+  const double h1 = P.h1(), h2 = P.h2(), eps = P.eps();
+  std::vector<double> a0(size_t(N + 1)), a1(size_t(N + 1)), b(size_t(N + 1));
+  auto a_row = [&](int64_t i, std::vector<double>& a) {
+    const double x = P.A1 + i * h1;
+    for (int64_t j = 1; j < N; ++j) {
+      const double y = P.A2 + j * h2;
+      a[size_t(j)] = face_coef(seg_len_vertical(x - 0.5 * h1, y - 0.5 * h2, y + 0.5 * h2, P.cx, P.cy, P.sx), h2, eps);
+    }
+  };
+  auto at = [&](int64_t i, int64_t j) {  // 0 on the box boundary
+    return (i < 1 || i > M - 1 || j < 1 || j > N - 1) ? 0.0 : v[(i - 1) * gny + (j - 1)];
+  };
+  double s = 0.0;
+  if (lo <= hi) a_row(lo, a1);
+  for (int64_t i = lo; i <= hi; ++i) {
+    a0.swap(a1);
+    a_row(i + 1, a1);
+    const double x = P.A1 + i * h1;
+    for (int64_t j = 1; j <= N; ++j) {
+      const double y = P.A2 + j * h2;
+      b[size_t(j)] = face_coef(seg_len_horizontal(y - 0.5 * h2, x - 0.5 * h1, x + 0.5 * h1, P.cx, P.cy, P.sy), h1, eps);
+    }
+    for (int64_t j = 1; j < N; ++j) {
+      const double c = at(i, j);
+      const double Ax = -1.0 / h1 * (a1[size_t(j)] * (at(i + 1, j) - c) / h1 - a0[size_t(j)] * (c - at(i - 1, j)) / h1);
+      const double Ay = -1.0 / h2 * (b[size_t(j + 1)] * (at(i, j + 1) - c) / h2 - b[size_t(j)] * (c - at(i, j - 1)) / h2);
+      const double Av = Ax + Ay;
+      double o = Av;
+      if (resid) {
+        const double y = P.A2 + j * h2;
+        const double Fij = rhs ? rhs[(i - 1) * gny + (j - 1)] : P.F;
+        o = (in_ellipse(x, y, P.cx, P.cy) ? Fij : 0.0) - Av;
+      }
+      if (out) out[(i - 1) * gny + (j - 1)] = o;
+      s += resid ? o * o : c * Av;
+    }
+  }
+  return s;
+}
+
+double operator_pass(const Problem& P, const double* v, bool resid, const double* rhs, double* out, int T,
+                     const char* what) {
+  if (!v) throw std::invalid_argument(std::string(what) + ": null array");
+  if (P.M < 2 || P.N < 2) throw std::invalid_argument(std::string(what) + ": grid too small");
+  const int64_t nx = int64_t(P.M) - 1;
+  if (T <= 1) return P.h1() * P.h2() * operator_rows(P, v, resid, rhs, out, 1, nx);
+  // thread t: the contiguous rows 1 + nx t / T .. nx (t + 1) / T; partials added in thread order
+  std::vector<double> part(size_t(T), 0.0);
+#pragma omp parallel for schedule(static, 1) num_threads(T)
+  for (int t = 0; t < T; ++t)
+    part[size_t(t)] = operator_rows(P, v, resid, rhs, out, 1 + (nx * t) / T, (nx * (t + 1)) / T);
+  double s = 0.0;
+  for (int t = 0; t < T; ++t) s += part[size_t(t)];
+  return P.h1() * P.h2() * s;
+}
+
+}  // namespace
+
+double apply_operator(const Problem& P, const double* v, double* out, int threads) {
+  return operator_pass(P, v, false, nullptr, out, threads, "apply_operator");
+}
+
+double residual_field(const Problem& P, const double* w, const double* rhs, double* out, int threads) {
+  return operator_pass(P, w, true, rhs, out, threads, "residual_field");
 }
 
 }  // namespace pe

@@ -245,6 +245,8 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
   PE_HIP_CHECK(hipMalloc(&rowcls_, sizeof(int) * nrow_tab * 4));
   PE_HIP_CHECK(hipMalloc(&halo_, sizeof(double) * hsize_ * 4));
   PE_HIP_CHECK(hipMalloc(&st_, sizeof(DevState)));
+  // (every reset zeroes the state again; an operator pass may run before the first one and needs ticket[3] == 0)
+  PE_HIP_CHECK(hipMemsetAsync(st_, 0, sizeof(DevState), stream_));
   PE_HIP_CHECK(hipHostMalloc(&hst_, sizeof(DevState) * 2, hipHostMallocDefault));
   std::memset(hst_, 0, sizeof(DevState) * 2);
   PE_HIP_CHECK(hipEventCreateWithFlags(&ev_[0], hipEventDisableTiming));
@@ -1244,6 +1246,76 @@ GradStats DeviceSolver::gradient_device(double* gx, double* gy, int64_t si, int6
   return g;
 }
 
+// The operator pass (kApplyField): the caller's global array is read in place —
+// no plane of the iteration is touched, scratch_used_ stays as it is.
+void DeviceSolver::check_apply_span(const void* v, int64_t si, int64_t sj, bool f32, const double* dst, int64_t dsi,
+                                    int64_t dsj, int64_t off_i, int64_t off_j) const {
+  if (!v) throw std::invalid_argument("field: null array");
+  if (si < 0 || sj < 0) throw std::invalid_argument("field: negative stride");
+  const int64_t gnx = int64_t(prob_.M) - 1, gny = int64_t(prob_.N) - 1;
+  check_device_span(v, (gnx - 1) * si + (gny - 1) * sj, f32 ? sizeof(float) : sizeof(double), "field");
+  if (!dst) return;
+  if (dsi < 0 || dsj < 0 || off_i < 0 || off_j < 0) throw std::invalid_argument("out: negative stride or offset");
+  // (the destination from its element [0][0] to this block's last element)
+  check_device_span(dst, (off_i + blk_.nx - 1) * dsi + (off_j + blk_.ny - 1) * dsj, sizeof(double), "out");
+}
+
+void DeviceSolver::enqueue_apply(const void* v, int64_t si, int64_t sj, bool f32, bool resid, double* dst, int64_t dsi,
+                                 int64_t dsj, int64_t off_i, int64_t off_j) {
+  dev::launch_apply_field(*kp_, v, f32, si, sj, resid, resid ? rhs_dev_ : nullptr, dst, dsi, dsj, off_i, off_j, stream_);
+  PE_HIP_CHECK(hipGetLastError());
+}
+
+double DeviceSolver::operator_pass(const void* v, int64_t si, int64_t sj, bool f32, bool resid, double* dst, int64_t dsi,
+                                   int64_t dsj, int64_t off_i, int64_t off_j, hipStream_t caller) {
+  check_apply_span(v, si, sj, f32, dst, dsi, dsj, off_i, off_j);
+  io_events();
+  PE_HIP_CHECK(hipEventRecord(ev_io_[0], caller));
+  PE_HIP_CHECK(hipStreamWaitEvent(stream_, ev_io_[0], 0));
+  enqueue_apply(v, si, sj, f32, resid, dst, dsi, dsj, off_i, off_j);
+  PE_HIP_CHECK(hipEventRecord(ev_io_[1], stream_));
+  PE_HIP_CHECK(hipStreamWaitEvent(caller, ev_io_[1], 0));
+  if (comm_->size() > 1) comm_->allreduce_sum(st_->res, 1, stream_);
+  DevState hs;
+  read_state(&hs);
+  return prob_.h1() * prob_.h2() * hs.res[0];
+}
+
+double DeviceSolver::apply_device(const void* v, int64_t si, int64_t sj, bool f32, double* dst, int64_t dsi, int64_t dsj,
+                                  int64_t off_i, int64_t off_j, hipStream_t caller) {
+  return operator_pass(v, si, sj, f32, false, dst, dsi, dsj, off_i, off_j, caller);
+}
+
+double DeviceSolver::residual_device(const void* w, int64_t si, int64_t sj, bool f32, double* dst, int64_t dsi,
+                                     int64_t dsj, int64_t off_i, int64_t off_j, hipStream_t caller) {
+  return operator_pass(w, si, sj, f32, true, dst, dsi, dsj, off_i, off_j, caller);
+}
+
+double DeviceSolver::operator_host(const double* v, double* out, bool resid) {
+  if (!v) throw std::invalid_argument("field: null array");
+  const int64_t gny = int64_t(prob_.N) - 1;
+  const size_t gn = size_t((int64_t(prob_.M) - 1) * gny), n = size_t(blk_.nx * blk_.ny);
+  double* d = nullptr;  // the global operand, then the owned result
+  PE_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&d), sizeof(double) * (gn + (out ? n : 0))));
+  double sum = 0.0;
+  try {
+    PE_HIP_CHECK(hipMemcpyAsync(d, v, sizeof(double) * gn, hipMemcpyHostToDevice, stream_));
+    sum = operator_pass(d, gny, 1, false, resid, out ? d + gn : nullptr, blk_.ny, 1, 0, 0, stream_);
+    if (out) {
+      PE_HIP_CHECK(hipMemcpyAsync(out, d + gn, sizeof(double) * n, hipMemcpyDeviceToHost, stream_));
+      PE_HIP_CHECK(hipStreamSynchronize(stream_));
+    }
+  } catch (...) {
+    (void)hipFree(d);
+    throw;
+  }
+  PE_HIP_CHECK(hipFree(d));
+  return sum;
+}
+
+double DeviceSolver::apply(const double* v, double* out) { return operator_host(v, out, false); }
+double DeviceSolver::residual(const double* w, double* out) { return operator_host(w, out, true); }
+
 void DeviceSolver::read_state(DevState* out) {
   PE_HIP_CHECK(hipMemcpyAsync(out, st_, sizeof(DevState), hipMemcpyDeviceToHost, stream_));
   PE_HIP_CHECK(hipStreamSynchronize(stream_));
@@ -1878,6 +1950,91 @@ SolveResult device_solve_group(const Problem& P, const ProcessGrid& pg, const So
   res.Py = pg.Py;
   res.t.solver = secs(t_start, clk::now());
   return res;
+}
+
+
+double device_apply_group(const Problem& P, const ProcessGrid& pg, const SolveOptions& opt, const OperatorFields& f,
+                          bool residual) {
+  if (!f.v && !f.v_host) throw std::invalid_argument("field: null array");
+  if (f.dst && f.host) throw std::invalid_argument("out: a host or a device destination, not both");
+  const int ranks = pg.Px * pg.Py;
+  const int64_t gny = int64_t(P.N) - 1, gn = (int64_t(P.M) - 1) * gny;
+  std::vector<std::unique_ptr<DeviceSolver>> s;
+  std::vector<Block> blks;
+  for (int r = 0; r < ranks; ++r) {
+    blks.push_back(decompose(P.M, P.N, pg, r));
+    s.push_back(std::make_unique<DeviceSolver>(P, blks.back(), nullptr, opt));
+    if (!residual) continue;
+    if (f.rhs) s.back()->set_rhs_device(f.rhs, f.rhs_si, f.rhs_sj, f.rhs_f32, f.stream);
+    else if (f.rhs_host) s.back()->set_rhs(block_field(f.rhs_host, P.M, P.N, blks.back(), 0).data());
+  }
+  hipStream_t s0 = s[0]->stream();
+  // staging: the host operand, and the result when only the host wants it
+  double* vbuf = nullptr;
+  double* obuf = nullptr;
+  double** dp = nullptr;
+  std::vector<hipEvent_t> ev(size_t(ranks), nullptr);
+  double sum = 0.0;
+  try {
+    const void* v = f.v;
+    int64_t si = f.v_si, sj = f.v_sj;
+    bool f32 = f.v_f32;
+    if (!v) {
+      PE_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&vbuf), sizeof(double) * size_t(gn)));
+      PE_HIP_CHECK(hipMemcpyAsync(vbuf, f.v_host, sizeof(double) * size_t(gn), hipMemcpyHostToDevice, s0));
+      v = vbuf, si = gny, sj = 1, f32 = false;
+    }
+    double* dst = f.dst;
+    int64_t dsi = f.dst_si, dsj = f.dst_sj;
+    if (!dst && f.host) {
+      PE_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&obuf), sizeof(double) * size_t(gn)));
+      dst = obuf, dsi = gny, dsj = 1;
+    }
+    // every refusal before any launch
+    for (int r = 0; r < ranks; ++r) s[r]->check_apply_span(v, si, sj, f32, dst, dsi, dsj, blks[r].i0 - 1, blks[r].j0 - 1);
+    for (auto& e : ev) PE_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    std::vector<double*> hp(static_cast<size_t>(ranks));
+    for (int r = 0; r < ranks; ++r) hp[size_t(r)] = s[r]->res_dev();
+    PE_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&dp), sizeof(double*) * size_t(ranks)));
+    PE_HIP_CHECK(hipMemcpyAsync(dp, hp.data(), sizeof(double*) * size_t(ranks), hipMemcpyHostToDevice, s0));
+    // s0 waits for the caller; every block's stream waits for s0 (the staged operand, the pointer table)
+    PE_HIP_CHECK(hipEventRecord(ev[0], f.stream));
+    PE_HIP_CHECK(hipStreamWaitEvent(s0, ev[0], 0));
+    PE_HIP_CHECK(hipEventRecord(ev[0], s0));
+    for (int r = 1; r < ranks; ++r) PE_HIP_CHECK(hipStreamWaitEvent(s[r]->stream(), ev[0], 0));
+    for (int r = 0; r < ranks; ++r)
+      s[r]->enqueue_apply(v, si, sj, f32, residual, dst, dsi, dsj, blks[r].i0 - 1, blks[r].j0 - 1);
+    for (int r = 1; r < ranks; ++r) {
+      PE_HIP_CHECK(hipEventRecord(ev[r], s[r]->stream()));
+      PE_HIP_CHECK(hipStreamWaitEvent(s0, ev[r], 0));
+    }
+    dev::launch_group_reduce(dp, ranks, 1, 0, s0);
+    PE_HIP_CHECK(hipGetLastError());
+    if (f.dst) {  // (s0 has joined every block's stream)
+      PE_HIP_CHECK(hipEventRecord(ev[0], s0));
+      PE_HIP_CHECK(hipStreamWaitEvent(f.stream, ev[0], 0));
+    }
+    DevState hs;
+    s[0]->read_state(&hs);  // (synchronizes s0)
+    sum = P.h1() * P.h2() * hs.res[0];
+    if (f.host) {
+      f.host->resize(size_t(gn));
+      PE_HIP_CHECK(hipMemcpy(f.host->data(), obuf, sizeof(double) * size_t(gn), hipMemcpyDeviceToHost));
+    }
+  } catch (...) {
+    (void)hipDeviceSynchronize();
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+    (void)hipFree(vbuf);
+    (void)hipFree(obuf);
+    (void)hipFree(dp);
+    throw;
+  }
+  for (auto& e : ev) PE_HIP_CHECK(hipEventDestroy(e));
+  PE_HIP_CHECK(hipFree(vbuf));
+  PE_HIP_CHECK(hipFree(obuf));
+  PE_HIP_CHECK(hipFree(dp));
+  return sum;
 }
 
 }  // namespace pe

@@ -793,6 +793,117 @@ __global__ __launch_bounds__(TJ) void kGradField(KParams k, const double* __rest
   }
 }
 
+// The operator applied to a user field, and the residual field of an iterate
+// (pe/fields.hpp apply_operator / residual_field, the same coefficients and
+// expression tree).  `g` is element [0][0] of the caller's GLOBAL interior
+// array (M−1) × (N−1), float64 or float32 (widened on load), element strides
+// (si, sj) ≥ 0: no staging plane, no halo exchange — a block's ring values are
+// its neighbours' entries of the same array, 0 on the box boundary.  Boundary
+// neighbours are loaded at the clamped in-range index and selected to 0, so no
+// load leaves the array.  kGradField's walk: tiles of kGradCols columns ×
+// `trows` rows dealt round-robin, one column per lane, kApplyU rows per step;
+// the rows above and below stay in registers, left / right neighbours are
+// re-read through the cache — 8 B read and (STORE) 8 B written per node when
+// sj == 1.  out = A v, or (RESID) B − A v with B = Bp (the user-rhs plane,
+// dense nx × ny; null: F) inside the ellipse and 0 outside, written like
+// kGatherW writes w.  Σ v·(A v) or (RESID) Σ out² over the owned nodes: block
+// partials → arrive_last → the last block in block order → st->res[0].
+// Reads tables only; of the state it writes res[0] and ticket[3].
+constexpr int kApplyU = 4;
+template <typename T>
+__device__ __forceinline__ double field_at(const T* col, int64_t si, int64_t gi, int64_t gnx, bool col_ok) {
+  const int64_t ci = gi < 1 ? 1 : (gi > gnx ? gnx : gi);  // (clamped: the load stays inside the array)
+  const double v = double(col[(ci - 1) * si]);
+  const bool ok = col_ok & (gi >= 1) & (gi <= gnx);  // (no short circuit: one select, the load above it stays unconditional)
+  return ok ? v : 0.0;
+}
+// … of an owned row (1 ≤ gi ≤ M−1): only the column can be off the box
+template <typename T>
+__device__ __forceinline__ double field_in_row(const T* col, int64_t si, int64_t gi, bool col_ok) {
+  const double v = double(col[(gi - 1) * si]);
+  return col_ok ? v : 0.0;
+}
+template <typename T, bool RESID, bool STORE>
+__global__ __launch_bounds__(TJ) void kApplyField(KParams k, const T* __restrict__ g, int64_t si, int64_t sj,
+                                                  const double* __restrict__ Bp, int trows, int64_t ctiles,
+                                                  int64_t ntiles, double* __restrict__ dst, int64_t dsi, int64_t dsj,
+                                                  int64_t off_i, int64_t off_j) {
+  __shared__ double sm[8];
+  __shared__ int sflag;
+  DevState* st = k.st;
+  const int64_t gnx = int64_t(k.M) - 1, gny = int64_t(k.N) - 1;
+  double acc = 0.0;
+  for (int64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    const int64_t band = t / ctiles, ct = t - band * ctiles;
+    const int64_t lj0 = ct * kGradCols + threadIdx.x + 1;
+    const bool live = lj0 <= k.ny;
+    const int64_t lj = live ? lj0 : k.ny;  // (idle lanes of the last column tile load in range, store nothing)
+    const int64_t gj = k.gj0 + lj;         // global node column, 1 .. N−1
+    const bool jm_ok = gj - 1 >= 1, jp_ok = gj + 1 <= gny;
+    // per-lane column pointers: this column, its left / right neighbour (clamped), the rhs plane, the destination
+    const T* pc = g + (gj - 1) * sj;
+    const T* pl = g + (jm_ok ? gj - 2 : 0) * sj;
+    const T* pr = g + (jp_ok ? gj : gny - 1) * sj;
+    const double y = k.A2 + gj * k.h2;
+    const double ty = k.cy * y * y;  // (in_ellipse's own products: cx x² + cy y² < 1)
+    const TV tv = tv_at(k, lj);
+    const int64_t li0 = band * trows + 1, li1 = min(k.nx, li0 + trows - 1);
+    // row li0 of this lane's column in the rhs plane (no plane: a table word is loaded instead and F selected,
+    // so the load is unconditional and queues with the others) and in the destination
+    const double* brow = Bp ? Bp + (li0 - 1) * k.ny + (lj - 1) : k.rowT;
+    const int64_t bstep = Bp ? k.ny : 0;
+    double* drow = STORE ? dst + (off_i + li0 - 1) * dsi + (off_j + lj - 1) * dsj : nullptr;
+    double wm = field_at(pc, si, k.gi0 + li0 - 1, gnx, true), wc = field_at(pc, si, k.gi0 + li0, gnx, true);
+    for (int64_t li = li0; li <= li1; li += kApplyU) {
+      // a batch of kApplyU rows of loads, all issued before the first row is computed: the row below (dn), the
+      // left / right neighbours (dl, dr), the rhs value (db).  Rows past the tile: clamped, loaded, unused.
+      double dn[kApplyU], dl[kApplyU], dr[kApplyU], db[RESID ? kApplyU : 1];
+#pragma unroll
+      for (int u = 0; u < kApplyU; ++u) {
+        const int64_t r = min(li + u, li1), gi = k.gi0 + r;
+        dn[u] = field_at(pc, si, gi + 1, gnx, true);
+        dl[u] = field_in_row(pl, si, gi, jm_ok);
+        dr[u] = field_in_row(pr, si, gi, jp_ok);
+        if constexpr (RESID) db[u] = brow[(r - li0) * bstep];
+      }
+#pragma unroll
+      for (int u = 0; u < kApplyU; ++u) {
+        const int64_t q = li + u;
+        if (q <= li1) {
+          const CS c = cset<true>(k, k.rowcls + (q + 1) * 4, q, lj, tv);
+          const double Av = stencil<true>(k, c, wm, wc, dn[u], dl[u], dr[u]);
+          double o = Av;
+          if constexpr (RESID) {
+            const double x = k.A1 + (k.gi0 + q) * k.h1;
+            const double B = k.cx * x * x + ty < 1.0 ? (Bp ? db[u] : k.F) : 0.0;
+            o = B - Av;
+          }
+          if (live) acc += RESID ? o * o : wc * Av;
+          if constexpr (STORE) {
+            if (live) *drow = o;
+            drow += dsi;
+          }
+          wm = wc;
+          wc = dn[u];
+        }
+      }
+    }
+  }
+  double s[1] = {acc};
+  block_reduce<1, false>(s, sm);
+  if (threadIdx.x == 0) k.partial[blockIdx.x] = s[0];
+  if (arrive_last(&st->ticket[3], gridDim.x, &sflag)) {
+    double a0 = 0.0;
+    for (unsigned b = threadIdx.x; b < gridDim.x; b += TJ) a0 += k.partial[b];
+    double s2[1] = {a0};
+    block_reduce<1, false>(s2, sm);
+    if (threadIdx.x == 0) {
+      st->res[0] = s2[0];
+      __hip_atomic_store(&st->ticket[3], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+}
+
 // p-plane of x[b] ← 0 over every allocated row and column (halos included):
 // rows 1-hdep .. nx+hdep+2, columns -xorg .. poff-xorg-1.
 __global__ __launch_bounds__(TJ) void kZeroP(KParams k, int b) {
@@ -996,6 +1107,34 @@ void launch_grad_field(const KParams& k, const double* plane, int64_t pitch, dou
     hipLaunchKernelGGL(kGradField<false>, grid, block, 0, s, k, plane, pitch, trows, ctiles, ntiles,
                        static_cast<double*>(nullptr), static_cast<double*>(nullptr), int64_t(0), int64_t(0), int64_t(0),
                        int64_t(0));
+}
+namespace {
+template <typename T, bool RESID>
+void apply_field_launch(const KParams& k, const T* g, int64_t si, int64_t sj, const double* rhs, double* dst,
+                        int64_t dsi, int64_t dsj, int64_t off_i, int64_t off_j, hipStream_t s) {
+  // launch_grad_field's tiling: ≈ 2048 tiles where the block has them, 8 .. 64 rows each, ≤ 4096 blocks
+  const int64_t ctiles = (k.ny + kGradCols - 1) / kGradCols;
+  const int64_t bands = std::max<int64_t>(1, 2048 / ctiles);
+  const int trows = int(std::max<int64_t>(8, std::min<int64_t>(64, (k.nx + bands - 1) / bands)));
+  const int64_t ntiles = ctiles * ((k.nx + trows - 1) / trows);
+  const dim3 grid(unsigned(std::min<int64_t>(ntiles, 4096))), block(TJ);
+  if (dst)
+    hipLaunchKernelGGL((kApplyField<T, RESID, true>), grid, block, 0, s, k, g, si, sj, rhs, trows, ctiles, ntiles, dst,
+                       dsi, dsj, off_i, off_j);
+  else
+    hipLaunchKernelGGL((kApplyField<T, RESID, false>), grid, block, 0, s, k, g, si, sj, rhs, trows, ctiles, ntiles,
+                       static_cast<double*>(nullptr), int64_t(0), int64_t(0), int64_t(0), int64_t(0));
+}
+}  // namespace
+void launch_apply_field(const KParams& k, const void* g, bool f32, int64_t si, int64_t sj, bool resid,
+                        const double* rhs, double* dst, int64_t dsi, int64_t dsj, int64_t off_i, int64_t off_j,
+                        hipStream_t s) {
+  const float* gf = static_cast<const float*>(g);
+  const double* gd = static_cast<const double*>(g);
+  if (f32 && resid) apply_field_launch<float, true>(k, gf, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
+  else if (f32) apply_field_launch<float, false>(k, gf, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
+  else if (resid) apply_field_launch<double, true>(k, gd, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
+  else apply_field_launch<double, false>(k, gd, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
 }
 void launch_zero_p(const KParams& k, int b, hipStream_t s) {
   hipLaunchKernelGGL(kZeroP, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, b);

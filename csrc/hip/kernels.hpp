@@ -329,6 +329,18 @@ void launch_resid(const KParams& k, int bw, bool with_r, bool store, hipStream_t
 // dst[(off_i + li) si + (off_j + lj) sj], li < nx, lj < ny.
 void launch_grad_field(const KParams& k, const double* plane, int64_t pitch, double* gx, double* gy, int64_t si,
                        int64_t sj, int64_t off_i, int64_t off_j, hipStream_t s);
+// kApplyField (pe/fields.hpp apply_operator / residual_field's device twin):
+// out = A v, or (resid) B − A v, on the owned nodes, v read directly from the
+// caller's GLOBAL interior array `g` ((M−1) × (N−1), element [0][0], element
+// strides (si, sj) ≥ 0, float64 or (f32) float32; ring values from the same
+// array, 0 on the box boundary).  B = `rhs` (the user right-hand side's device
+// plane, dense nx × ny; null: F) inside the ellipse, 0 outside.  The field is
+// written as kGatherW writes w (dst null: the sum only); Σ v·(A v) or (resid)
+// Σ out² → st->res[0], block partials summed in block order.  Reads tables
+// only: valid in every layout, before or after a solve or a gradient pass.
+void launch_apply_field(const KParams& k, const void* g, bool f32, int64_t si, int64_t sj, bool resid,
+                        const double* rhs, double* dst, int64_t dsi, int64_t dsj, int64_t off_i, int64_t off_j,
+                        hipStream_t s);
 // Classic layout, for kGradField: owned w → the r plane and its y strips →
 // send_dn / send_up (what halo_plan() exchanges); then recv_dn / recv_up →
 // columns 0 / ny+1 of the r plane.  Both clobber r: only a reset may follow.

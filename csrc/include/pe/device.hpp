@@ -320,6 +320,38 @@ class DeviceSolver {
   void enqueue_grad_stage();
   void enqueue_grad(double* gx, double* gy, int64_t si, int64_t sj, int64_t off_i, int64_t off_j);
   double* res_dev();
+  // The operator applied to a user field, and the residual field of an iterate
+  // (pe/fields.hpp apply_operator / residual_field; kApplyField).  `v` / `w`
+  // points at element [0][0] of the GLOBAL interior array (M-1) × (N-1) on
+  // this solver's device, float64 or (f32) float32, element strides (si, sj)
+  // ≥ 0; on a multi-rank job every rank holds the global array, as for rhs.
+  // This block's owned part of A v — or of B − A w, B the rhs set by set_rhs /
+  // set_rhs_device (else F) inside the ellipse and 0 outside — is written into
+  // float64 device memory as copy_w_device writes w, dst[(off_i + li) dsi +
+  // (off_j + lj) dsj] (dst null: the sum only).  Returns the job's
+  // h1·h2·Σ v·(A v), or h1·h2·Σ (B − A w)²: collective on a multi-rank job.
+  // Events only: the solver stream waits for `caller`, `caller` waits for the
+  // kernel.  Source and destination get copy_w_device's pointer check before
+  // any launch (std::invalid_argument; nothing is changed).  The pass reads
+  // the solver's tables only — no iteration plane, not w: it may run before a
+  // solve, after one and after a gradient pass, and the next solve is the
+  // same solve.
+  double apply_device(const void* v, int64_t si, int64_t sj, bool f32, double* dst, int64_t dsi, int64_t dsj,
+                      int64_t off_i, int64_t off_j, hipStream_t caller);
+  double residual_device(const void* w, int64_t si, int64_t sj, bool f32, double* dst, int64_t dsi, int64_t dsj,
+                         int64_t off_i, int64_t off_j, hipStream_t caller);
+  // The same from / to host memory: `v` / `w` the global (M-1)(N-1) array,
+  // `out` the owned nx × ny part (null: the sum only); staged through device
+  // buffers freed at return.
+  double apply(const double* v, double* out);
+  double residual(const double* w, double* out);
+  // Their phases, for the virtual-rank group driver: the refusal (throws
+  // std::invalid_argument unless source and destination are device memory of
+  // this solver's device over their whole extent), and the kernel → res_dev()[0].
+  void check_apply_span(const void* v, int64_t si, int64_t sj, bool f32, const double* dst, int64_t dsi, int64_t dsj,
+                        int64_t off_i, int64_t off_j) const;
+  void enqueue_apply(const void* v, int64_t si, int64_t sj, bool f32, bool resid, double* dst, int64_t dsi, int64_t dsj,
+                     int64_t off_i, int64_t off_j);
   // gradient_device()'s refusal: throws std::invalid_argument unless both destinations are device memory of this
   // solver's device from element [0][0] to this block's last element
   void check_grad_span(const double* gx, const double* gy, int64_t si, int64_t sj, int64_t off_i, int64_t off_j) const;
@@ -382,6 +414,10 @@ class DeviceSolver {
   void residual_pass(bool with_r, bool store);
   // gradient() / gradient_device(): stage, halo exchange, kernel, cross-rank reductions, state read
   GradStats gradient_pass(double* gx, double* gy, int64_t si, int64_t sj, int64_t off_i, int64_t off_j);
+  // apply_device() / residual_device(): check, events, kernel, cross-rank sum, state read
+  double operator_pass(const void* v, int64_t si, int64_t sj, bool f32, bool resid, double* dst, int64_t dsi,
+                       int64_t dsj, int64_t off_i, int64_t off_j, hipStream_t caller);
+  double operator_host(const double* v, double* out, bool resid);  // apply() / residual()
   void wait_event(hipEvent_t ev);  // event wait with transport-error polling + watchdog
   void enqueue_chunk(int iters, int sample_iters = 0);
   // Sampled phase timing (Timers): hipEvent pairs around the phases of the
@@ -548,6 +584,31 @@ struct GroupGradient {
   bool stats = false;
   std::vector<double>* host = nullptr;
 };
+// device_apply_group: the operand v (or the iterate w) and, for the residual,
+// a user right-hand side (neither form: F) as global interior arrays in host or
+// device memory (a field given both ways is taken from the device); A v (or
+// B − A w) into one global (M-1) × (N-1) destination in device memory, every
+// block's solver writing its position, and / or into `host` (row-major).
+struct OperatorFields {
+  const double* v_host = nullptr;
+  const void* v = nullptr;  // element [0][0], strides in elements, float64 or float32
+  int64_t v_si = 0, v_sj = 0;
+  bool v_f32 = false;
+  const double* rhs_host = nullptr;
+  const void* rhs = nullptr;
+  int64_t rhs_si = 0, rhs_sj = 0;
+  bool rhs_f32 = false;
+  double* dst = nullptr;
+  int64_t dst_si = 0, dst_sj = 0;
+  std::vector<double>* host = nullptr;
+  hipStream_t stream = nullptr;  // the caller's stream (producer of v and rhs, consumer of dst)
+};
+// P virtual ranks on one device apply the operator (residual: form B − A w):
+// every block's kApplyField reads the one global array — the seams between
+// blocks get their neighbours' values from it — and the blocks' sums go
+// through the group reduction.  Returns h1·h2·Σ.
+double device_apply_group(const Problem& prob, const ProcessGrid& pg, const SolveOptions& opt,
+                          const OperatorFields& fields, bool residual);
 SolveResult device_solve_group(const Problem& prob, int ranks, DecompMode mode, const SolveOptions& opt,
                                std::vector<double>* w_out = nullptr, const UserFields& fields = UserFields());
 SolveResult device_solve_group(const Problem& prob, const ProcessGrid& pg, const SolveOptions& opt,

@@ -62,4 +62,20 @@ struct GradStats {
 // the same shape (both null: the functionals only).  Host only.
 GradStats gradient_field(const Problem& prob, const double* w, double* gx, double* gy);
 
+// The fictitious-domain operator applied to a user field, and the residual
+// field of an iterate — one definition for every backend (the device kernel
+// kApplyField is its twin).  Coefficients a, b = face_coef(seg_len_*) as the
+// CPU solver's assemble() forms them; the expression is its apply_A's tree,
+// Ax + Ay, the reference's.  Sums run in row-major order; threads > 1 splits
+// the rows as the CPU solver's row_sum does (thread partials added in thread order).
+//
+// out = A v over the global interior (M−1) × (N−1); v is 0 on the box boundary.
+// Every interior node, inside or outside the ellipse (the fictitious-domain
+// system has unknowns everywhere).  Returns h1·h2·Σ v·(A v).  `out` may be
+// null: the sum only.
+double apply_operator(const Problem& prob, const double* v, double* out, int threads = 1);
+// out = B − A w, B = rhs (null: F) at nodes inside the ellipse, 0 elsewhere
+// (assemble()'s mask).  Returns h1·h2·Σ out².  `out` may be null.
+double residual_field(const Problem& prob, const double* w, const double* rhs, double* out, int threads = 1);
+
 }  // namespace pe

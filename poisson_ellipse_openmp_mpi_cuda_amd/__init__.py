@@ -19,7 +19,7 @@ Subpackages: ``models`` (problem definitions), ``ops`` (kernels / oracle),
 """
 
 from .models.ellipse import EllipseProblem, REFERENCE_PROBLEM  # noqa: F401
-from .solver import solve, SolveReport, DeviceSession  # noqa: F401
+from .solver import solve, SolveReport, DeviceSession, FieldResult, apply_operator, residual  # noqa: F401
 from ._loader import native, native_available  # noqa: F401
 
 __version__ = "0.1.0"

@@ -33,6 +33,11 @@ h1 h2 Σ_D |∇w|² and max_D |∇w| on a line of their own after the result lin
 
     python -m poisson_ellipse_openmp_mpi_cuda_amd.cli --grad-stats --dump-grad g.npy 400 600
 
+``--dump-resid FILE.npy`` writes the residual field B − A w of the solve's w
+(float64 (M-1, N-1), the shape of ``--dump``) and prints ‖B − A w‖_E on a line
+of its own — the stop test is the step size, so this is where to look for
+what the iterate still misses.
+
 Checkpoints hold the iteration state, not the fields: ``--resume`` needs the
 same ``--rhs`` (and ``--exact``) again, and ignores ``--w0``.
 """
@@ -40,13 +45,14 @@ same ``--rhs`` (and ``--exact``) again, and ignores ``--w0``.
 from __future__ import annotations
 
 import argparse
+import math
 import os
 import sys
 
 import numpy as np
 
 from .models.ellipse import PRESETS, EllipseProblem
-from .solver import BACKENDS, solve, user_field
+from .solver import BACKENDS, residual, solve, user_field
 from .utils import dump as _dump
 from .utils.report import json_report, legacy_lines
 
@@ -97,6 +103,9 @@ def build_parser():
                     help="write the gradient of w inside the ellipse, float64 (2, M-1, N-1): [0] d/dx, [1] d/dy")
     ap.add_argument("--grad-stats", action="store_true",
                     help="print h1 h2 sum_D w, h1 h2 sum_D |grad w|^2 and max_D |grad w| after the result lines")
+    ap.add_argument("--dump-resid", default=None, metavar="FILE.npy",
+                    help="write the residual field B - A w of the solve's w, float64 (M-1, N-1) like --dump, and "
+                         "print its E-norm on a line of its own")
     return ap
 
 
@@ -108,7 +117,7 @@ def main(argv=None) -> int:
     prob.tol = a.tol
     prob.max_iter = a.max_iter
     prob.norm = a.norm
-    want_w = bool(a.dump or a.pgm)
+    want_w = bool(a.dump or a.pgm or a.dump_resid)
     try:
         rhs = None if a.rhs is None else user_field("--rhs", np.load(a.rhs, allow_pickle=False), prob)
         w0 = None if a.w0 is None else user_field("--w0", np.load(a.w0, allow_pickle=False), prob)
@@ -133,6 +142,16 @@ def main(argv=None) -> int:
     if a.grad_stats:
         print(f"   Integral of w in D ~ {rep.integral:.6e} | energy ~ {rep.energy:.6e} | max |grad w| in D ~ "
               f"{rep.grad_max:.6e}")
+    if a.dump_resid and rep.w is not None:
+        # the backend's own operator pass where this process is the whole job; the host definition otherwise (the
+        # gathered w lives on rank 0 only)
+        from .parallel.dist import env_rank_world
+
+        alone = a.backend not in ("hip", "dist-cpu") or env_rank_world()[1] == 1
+        res = residual(prob, rep.w, rhs, backend=a.backend if alone else "omp", ranks=a.ranks, threads=a.threads,
+                       decomp=a.decomp)
+        np.save(a.dump_resid, res.field)
+        print(f"   Residual ||B - A w||_E ~ {math.sqrt(res.sum):.6e}")
     if a.json:
         print(json_report(rep))
     if a.dump_grad and rep.grad is not None:

@@ -119,6 +119,14 @@ def apply_A(p, a, b, h1, h2):
     return out
 
 
+def residual(prob: EllipseProblem, W, rhs=None, device="cpu"):
+    """B − A W as an (M+1, N+1) tensor (0 on the box boundary): W an interior
+    (M-1, N-1) array or a full tensor, B = rhs (None: F) inside the ellipse
+    and 0 outside — the torch form of native.residual_field."""
+    a, b, B = assemble(prob, device, rhs=rhs)
+    return B - apply_A(embed(prob, W, device), a, b, prob.h1, prob.h2)
+
+
 def diag(a, b, h1, h2):
     """Jacobi diagonal D on interior nodes (0 elsewhere)."""
     D = torch.zeros_like(a)

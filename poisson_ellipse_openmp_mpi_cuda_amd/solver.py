@@ -106,6 +106,19 @@ class SolveReport:
         return d
 
 
+@dataclasses.dataclass
+class FieldResult:
+    """What apply_operator() / residual() return.  ``field``: A v (or B − A w) over
+    the global interior, float64 (M-1, N-1) — numpy (out="host"; None on the
+    ranks of a multi-process job other than 0), a GPU tensor (out="device"; on a
+    multi-process ``hip`` job this rank's owned block, ``origin`` = (i0, j0) the
+    global 1-based node index of its first entry) or None (out="sum").
+    ``sum``: h1·h2·Σ v·(A v), or h1·h2·Σ (B − A w)² = ‖B − A w‖²_E."""
+    field: object
+    sum: float
+    origin: Optional[tuple] = None
+
+
 ALGOS = {"auto": 0, "classic": 1, "fused": 2, "two-step": 3, "three-step": 4}
 
 
@@ -401,6 +414,74 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
         return session._solve(rhs, w0, return_w, exact, grad)
 
 
+def _out_mode(out, on_device: bool, backend: str = "hip") -> str:
+    if out not in ("host", "device", "sum"):
+        raise ValueError('out must be "host", "device" or "sum"')
+    if out == "device" and not on_device:
+        raise ValueError(f'out="device" needs backend "hip" or "hip-group", not "{backend}"')
+    return out
+
+
+def _operator(prob, v, rhs, residual_, backend, ranks, threads, decomp, out, device, kw) -> FieldResult:
+    """apply_operator() / residual() on every backend."""
+    name = "w" if residual_ else "v"
+    if backend not in BACKENDS:
+        raise ValueError(f"backend must be one of {BACKENDS}")
+    on_device = backend in ("hip", "hip-group")
+    out = _out_mode(out, on_device, backend)
+    if v is None:
+        raise ValueError(f"{name}: a field is required")
+    v = _field_arg(name, v, prob, on_device)
+    rhs = _field_arg("rhs", rhs, prob, on_device) if residual_ else None
+    nat = native()
+    P = prob.to_native()
+    want = out != "sum"
+    if backend in ("serial", "omp", "ranks", "dist-cpu"):
+        # the host definition on the global array (every rank of a dist-cpu job holds it: no communication)
+        t = 1 if backend == "serial" else max(1, threads)
+        s, f = nat.residual_field(P, v, rhs, want, t) if residual_ else nat.apply_operator(P, v, want, t)
+        rank = 0
+        if backend == "dist-cpu":
+            from .parallel import dist as _dist
+
+            rank = _dist.init().rank
+        return FieldResult(np.asarray(f) if want and rank == 0 else None, float(s))
+    if backend == "torch":
+        import torch
+
+        from .ops import torch_ref
+
+        if device.startswith("cuda") and not torch.cuda.is_available():
+            device = "cpu"
+        V = torch_ref.embed(prob, v, device)
+        if residual_:
+            f = torch_ref.residual(prob, V, rhs, device)[1:-1, 1:-1]
+            s = float((f * f).sum())
+        else:
+            a, b, _ = torch_ref.assemble(prob, device)
+            f = torch_ref.apply_A(V, a, b, prob.h1, prob.h2)[1:-1, 1:-1]
+            s = float((V[1:-1, 1:-1] * f).sum())
+        return FieldResult(f.cpu().numpy() if want else None, prob.h1 * prob.h2 * s)
+    if backend == "hip-group":
+        import torch
+
+        opt = _options(chunk=kw.get("chunk", 0), variant=kw.get("variant", 0), algo=kw.get("algo", "auto"))
+        pg = _decomp.grid(ranks, prob.M, prob.N, decomp or _decomp.default_spec(backend))
+        index = nat.current_device()
+        fields = ((name, v), ("rhs", rhs))
+        dev = {n: device_field(n, f, prob, index) for n, f in fields if is_device_tensor(f)}
+        host = {n: f for n, f in fields if n not in dev}
+        ot = o_dev = None
+        if out == "device":  # every block's kernel writes its position of this one tensor
+            ot = torch.empty((prob.M - 1, prob.N - 1), dtype=torch.float64, device=f"cuda:{index}")
+            o_dev = (ot.data_ptr(), ot.stride(0), ot.stride(1))
+        s, f = nat.device_apply_group(P, pg, opt, residual_, host.get(name), dev.get(name), host.get("rhs"),
+                                      dev.get("rhs"), o_dev, out == "host", _stream_handle(index))
+        return FieldResult(ot if ot is not None else (np.asarray(f) if f is not None else None), float(s))
+    with DeviceSession(prob, decomp, **kw) as session:
+        return session._operator(v, rhs, residual_, out, set_rhs=True)
+
+
 _HIP_OPTIONS = ("chunk", "graph", "timing", "check_tol", "variant", "algo", "checkpoint_every", "checkpoint", "resume",
                 "keep_history", "log_every")
 
@@ -473,6 +554,80 @@ class DeviceSession:
         grad = _grad_mode(return_grad, True)
         return self._solve(_field_arg("rhs", rhs, self.prob, True), _field_arg("w0", w0, self.prob, True), return_w,
                            _field_arg("exact", exact, self.prob, True), grad)
+
+    def apply(self, v, out="host") -> FieldResult:
+        """A v for a field of the caller's on the kept solver.  ``v``: a host array
+        or a GPU tensor of the global interior, in the forms ``rhs`` takes
+        (float64 or float32, any strides, shape (M-1, N-1), on ``device_index``).
+        ``out``: "host" (numpy; on a multi-process job gathered onto rank 0),
+        "device" (a float64 GPU tensor written by the kernel; on a multi-process
+        job this rank's block at ``origin``) or "sum" (no field).  The result's
+        ``sum`` is h1·h2·Σ v·(A v).  The pass reads the solver's tables only: the
+        next solve is the same solve."""
+        return self._operator(_field_arg("v", v, self.prob, True), None, False, _out_mode(out, True))
+
+    _KEEP = object()
+
+    def residual(self, w, rhs=_KEEP, out="host") -> FieldResult:
+        """B − A w for an iterate of the caller's; ``sum`` is ‖B − A w‖²_E.
+        ``rhs``: per call, as in solve(rhs=) — a field, or None for F; left out,
+        the right-hand side of the last solve() / residual() stays.  ``w`` and
+        ``out`` as in apply()."""
+        if w is None:
+            raise ValueError("w: a field is required")
+        keep = rhs is DeviceSession._KEEP
+        return self._operator(_field_arg("w", w, self.prob, True),
+                              None if keep else _field_arg("rhs", rhs, self.prob, True), True, _out_mode(out, True),
+                              set_rhs=not keep)
+
+    def _operator(self, v, rhs, residual_, out, set_rhs=False) -> FieldResult:
+        # v / rhs: checked host arrays or GPU tensors of checked shape and dtype (_field_arg)
+        from .parallel import dist as _dist
+
+        if self.solver is None:
+            raise RuntimeError("DeviceSession is closed")
+        if v is None:
+            raise ValueError("v: a field is required")
+        nat, s, prob, blk, comm = native(), self.solver, self.prob, self.block, self.comm
+        name = "w" if residual_ else "v"
+        # every refusal before anything is set or launched
+        spec = device_field(name, v, prob, self.device_index) if is_device_tensor(v) else None
+        rspec = device_field("rhs", rhs, prob, self.device_index) if is_device_tensor(rhs) else None
+        try:
+            if residual_ and set_rhs:
+                if rspec is not None:
+                    s.set_rhs_device(*rspec, _stream_handle(self.device_index))
+                else:
+                    s.set_rhs(None if rhs is None else nat.block_fields(prob.M, prob.N, blk, rhs, None)[0])
+            f = origin = None
+            if out == "device" or spec is not None:
+                import torch
+
+                stream = _stream_handle(self.device_index)
+                if spec is None:  # a host array: one upload, then the device path
+                    t = torch.tensor(v, device=f"cuda:{self.device_index}")
+                    spec = tensor_spec(name, t, prob)
+                dst = (0, 0, 0)
+                if out != "sum":
+                    f = torch.empty((blk.nx, blk.ny), dtype=torch.float64, device=f"cuda:{self.device_index}")
+                    dst = (f.data_ptr(), f.stride(0), f.stride(1))
+                total = s.apply_device(*spec, residual_, *dst, 0, 0, stream)
+                if out == "device" and self.world > 1:
+                    origin = (int(blk.i0), int(blk.j0))
+                if out == "host":
+                    f = f.cpu().numpy()
+            else:
+                total, f = s.apply(v, residual_, out == "host")
+                f = None if f is None else np.asarray(f)
+            if out == "host" and self.world > 1:
+                f = _dist.gather_blocks(_dist.init(), prob, blk, f)
+        except ValueError:
+            raise  # (a refused field: nothing was launched, the session stays usable)
+        except Exception:
+            if comm is not None:
+                _dist.drop_comm(comm)
+            raise
+        return FieldResult(f, float(total), origin)
 
     def _set_fields(self, rhs, w0, exact=None) -> None:
         """The three fields into the solver's planes; everything is checked
@@ -567,3 +722,26 @@ class DeviceSession:
         rep.sums = str(s.xr_status)
         rep.peer_access = [int(v) for v in s.peer_access]
         return rep
+
+
+def apply_operator(prob: EllipseProblem, v, backend: str = "hip", ranks: int = 1, threads: int = 1,
+                   decomp: str | None = None, out: str = "host", device: str = "cuda", **kw) -> FieldResult:
+    """A v: the fictitious-domain operator (coefficients and expression of the
+    solve) applied to a field of the caller's.  ``v``: the global interior,
+    shape (M-1, N-1), 0 on the box boundary — a host array on every backend, or
+    on ``hip`` / ``hip-group`` a GPU tensor in the forms ``rhs`` takes.  A v is
+    taken at every interior node, inside or outside the ellipse.  ``out``:
+    "host" (numpy), "device" (``hip`` / ``hip-group``: a float64 GPU tensor
+    written by the kernel) or "sum" (no field); the result's ``sum`` is
+    h1·h2·Σ v·(A v).  Every backend gives the definition of
+    csrc/include/pe/fields.hpp; DeviceSession.apply() serves a sequence of
+    calls from one constructed solver."""
+    return _operator(prob, v, None, False, backend, ranks, threads, decomp, out, device, kw)
+
+
+def residual(prob: EllipseProblem, w, rhs=None, backend: str = "hip", ranks: int = 1, threads: int = 1,
+             decomp: str | None = None, out: str = "host", device: str = "cuda", **kw) -> FieldResult:
+    """B − A w for an iterate of the caller's: B = ``rhs`` (None: F) inside the
+    ellipse and 0 outside, as solve() masks it.  ``sum`` is h1·h2·Σ (B − A w)²,
+    the square of the E-norm of the residual.  Arguments as apply_operator()."""
+    return _operator(prob, w, rhs, True, backend, ranks, threads, decomp, out, device, kw)
