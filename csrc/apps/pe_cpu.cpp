@@ -4,7 +4,9 @@
 //          [--threads-sweep 1,4,16] [--norm weighted|unweighted]
 //          [--decomp reference|aspect] [--init zero|random] [--seed S]
 //          [--tol 1e-6] [--max-iter K] [--stage stage0|stage1|stage2|stage3]
-//          [--json] [M N]
+//          [--shift S] [--json] [M N]
+// --shift S (finite, >= 0) solves (A + S·I) w = B, −Δu + S·u = f; the analytic
+// error then reads n/a and --json carries "shift".
 // Replaces: stage0/Withoutopenmp*.cpp main (:176-196), stage1 thread sweep
 // (Withopenmp2.cpp:204-229), stage2/3 mpirun runs (poisson_mpi_decomp.cpp:463-502,
 // main_hybrid.cpp:473-512) — ranks are threads here (no MPI needed).
@@ -31,7 +33,8 @@ int main(int argc, char** argv) {
   if (args.flag("help")) {
     std::puts("usage: pe_cpu [--backend serial|omp|ranks] [--ranks P] [--threads T] [--threads-sweep L]\n"
               "              [--norm weighted|unweighted] [--decomp reference|aspect] [--init zero|random]\n"
-              "              [--seed S] [--tol D] [--max-iter K] [--stage stage0..3] [--grids 10,20,40] [--json] [M N]");
+              "              [--seed S] [--tol D] [--max-iter K] [--stage stage0..3] [--grids 10,20,40] [--shift S]\n"
+              "              [--json] [M N]");
     return 0;
   }
   Problem P;
@@ -42,6 +45,16 @@ int main(int argc, char** argv) {
   }
   P.tol = args.getd("tol", 1e-6);
   P.max_iter = args.geti("max-iter", -1);
+  P.shift = args.getd("shift", 0.0);
+  try {
+    check_shift(P, "pe_cpu");
+  } catch (const std::invalid_argument& e) {
+    std::fprintf(stderr, "%s\n", e.what());
+    return 2;
+  }
+  // ("shift" only when non-zero: the unshifted output stays byte for byte)
+  char shift_json[64] = "";
+  if (P.shift != 0.0) std::snprintf(shift_json, sizeof(shift_json), ", \"shift\": %.17g", P.shift);
   const std::string backend = args.get("backend", "serial");
   std::string stage = args.get("stage", "");
   // stage0 (Withoutopenmp1.cpp:106-196) stops on the unweighted ‖Δw‖ and, run
@@ -78,15 +91,18 @@ int main(int argc, char** argv) {
       std::printf("{\"M\": %d, \"N\": %d, \"backend\": \"%s\", \"ranks\": %d, \"threads\": %d, \"Px\": %d, \"Py\": %d, "
                   "\"iters\": %lld, \"converged\": %s, \"t_solver\": %.6f, \"t_iterate\": %.6f, \"t_halo\": %.6f, "
                   "\"t_reduce\": %.6f, \"t_prec\": %.6f, \"t_dot\": %.6f, \"l2_err\": %.6e, \"max_err\": %.6e, "
-                  "\"max_outside\": %.6e}\n",
+                  "\"max_outside\": %.6e%s}\n",
                   P.M, P.N, r.backend.c_str(), ranks, t, r.Px, r.Py, (long long)r.iters,
                   r.converged ? "true" : "false", r.t.solver, r.t.iterate, r.t.halo, r.t.reduce, r.t.prec,
-                  r.t.dot, r.l2_err, r.max_err, r.max_outside);
+                  r.t.dot, r.l2_err, r.max_err, r.max_outside, shift_json);
     } else {
       if (sweep.size() > 1) std::printf("Threads = %2d | Time = %.3f s | Iter=%lld\n", t, r.t.solver, (long long)r.iters);
       else std::cout << format_result_legacy(P, r, ranks, stage);
-      std::printf("   L2 error in D ~ %.6e   max error in D ~ %.6e   max |w| outside D ~ %.3e\n", r.l2_err,
-                  r.max_err, r.max_outside);
+      if (P.shift != 0.0)
+        std::printf("   L2 error in D ~ n/a (shifted operator)   max |w| outside D ~ %.3e\n", r.max_outside);
+      else
+        std::printf("   L2 error in D ~ %.6e   max error in D ~ %.6e   max |w| outside D ~ %.3e\n", r.l2_err,
+                    r.max_err, r.max_outside);
     }
   }
   return 0;

@@ -2,14 +2,15 @@
 // value encodes (i, j) and checks it node by node — the owned parts tile the
 // interior, the rings hold the neighbours' values and zeros on the box
 // boundary.  Then pe::gradient_field, pe::apply_operator and
-// pe::residual_field on two small grids against their definitions written
-// out.  No device: the sanitizer build's driver of pe/fields.hpp (make asan).
+// pe::residual_field (unshifted and with Problem::shift) on two small grids
+// against their definitions written out.  No device: the sanitizer build's driver of pe/fields.hpp (make asan).
 //   pe_fields M N PX PY
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <stdexcept>
 #include <vector>
 
 #include "pe/fields.hpp"
@@ -61,8 +62,11 @@ static int64_t check_gradient(const pe::Problem& P) {
 // Mismatches of pe::apply_operator / pe::residual_field on P's grid against a
 // naive double loop over full coefficient arrays and a zero-padded copy of a
 // field that is non-zero everywhere; one and three threads, with and without
-// a destination, built-in F and a user right-hand side.
-static int64_t check_operator(const pe::Problem& P) {
+// a destination, built-in F and a user right-hand side; the unshifted operator
+// and A + σI for two shifts (A_σ v = (Ax + Ay) + σ·v written out), and the
+// refusal of a negative or non-finite shift.
+static int64_t check_operator(const pe::Problem& P0) {
+  const pe::Problem& P = P0;
   const int64_t M = P.M, N = P.N, gny = N - 1, n = (M - 1) * gny, C = N + 2;
   const double h1 = P.h1(), h2 = P.h2(), eps = P.eps();
   std::vector<double> v(static_cast<size_t>(n)), f(v.size());
@@ -80,7 +84,19 @@ static int64_t check_operator(const pe::Problem& P) {
       }
     }
   int64_t bad = 0;
+  for (const double wrong : {-1.0, std::nan(""), HUGE_VAL}) {
+    pe::Problem Q = P0;
+    Q.shift = wrong;
+    try {
+      pe::apply_operator(Q, v.data(), nullptr, 1);
+      ++bad;
+    } catch (const std::invalid_argument&) {
+    }
+  }
+  for (const double sigma : {0.0, 0.75, 40.0})
   for (int mode = 0; mode < 3; ++mode) {  // 0: A v; 1: F − A v; 2: f − A v
+    pe::Problem P = P0;
+    P.shift = sigma;
     const double* rhs = mode == 2 ? f.data() : nullptr;
     std::vector<double> want(v.size());
     double s = 0.0;
@@ -90,6 +106,7 @@ static int64_t check_operator(const pe::Problem& P) {
         const double Ax = -1.0 / h1 * (a[size_t(c + C)] * (V[size_t(c + C)] - V[size_t(c)]) / h1 - a[size_t(c)] * (V[size_t(c)] - V[size_t(c - C)]) / h1);
         const double Ay = -1.0 / h2 * (b[size_t(c + 1)] * (V[size_t(c + 1)] - V[size_t(c)]) / h2 - b[size_t(c)] * (V[size_t(c)] - V[size_t(c - 1)]) / h2);
         double r = Ax + Ay;
+        if (sigma != 0.0) r = r + sigma * V[size_t(c)];
         if (mode) {
           const bool in = pe::in_ellipse(P.A1 + i * h1, P.A2 + j * h2, P.cx, P.cy);
           r = (in ? (rhs ? rhs[size_t(o)] : P.F) : 0.0) - r;
@@ -158,6 +175,7 @@ int main(int argc, char** argv) {
   const int64_t gbad = check_gradient(ref) + check_gradient(tiny);
   std::printf("pe_fields gradient_field 10x50, 12x12 (cx = cy = 30): %s\n", gbad ? "MISMATCH" : "ok");
   const int64_t obad = check_operator(ref) + check_operator(tiny);
-  std::printf("pe_fields apply_operator / residual_field 10x50, 12x12 (cx = cy = 30): %s\n", obad ? "MISMATCH" : "ok");
+  std::printf("pe_fields apply_operator / residual_field 10x50, 12x12 (cx = cy = 30), shift 0, 0.75, 40: %s\n",
+              obad ? "MISMATCH" : "ok");
   return bad || gbad || obad ? 1 : 0;
 }

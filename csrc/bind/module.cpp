@@ -151,6 +151,7 @@ PYBIND11_MODULE(_native, m) {
       .def_readwrite("tol", &Problem::tol)
       .def_readwrite("max_iter", &Problem::max_iter)
       .def_readwrite("norm", &Problem::norm)
+      .def_readwrite("shift", &Problem::shift)
       .def("h1", &Problem::h1)
       .def("h2", &Problem::h2)
       .def("eps", &Problem::eps)

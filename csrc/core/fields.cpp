@@ -10,6 +10,12 @@
 
 namespace pe {
 
+void check_shift(const Problem& P, const char* who) {
+  if (!std::isfinite(P.shift) || P.shift < 0.0)
+    throw std::invalid_argument(std::string(who) + ": shift must be finite and >= 0 (got " + std::to_string(P.shift) +
+                                "): a negative shift makes the system indefinite");
+}
+
 std::vector<double> block_field(const double* g, int M, int N, const Block& blk, int ring) {
   if (!g) throw std::invalid_argument("block_field: null array");
   if (ring != 0 && ring != 1) throw std::invalid_argument("block_field: ring must be 0 or 1");
@@ -85,6 +91,7 @@ double operator_rows(const Problem& P, const double* v, bool resid, const double
                      int64_t hi) {
   const int64_t M = P.M, N = P.N, gny = N - 1;
   const double h1 = P.h1(), h2 = P.h2(), eps = P.eps();
+  const bool shifted = P.shift != 0.0;
   std::vector<double> a0(size_t(N + 1)), a1(size_t(N + 1)), b(size_t(N + 1));
   auto a_row = [&](int64_t i, std::vector<double>& a) {
     const double x = P.A1 + i * h1;
@@ -110,7 +117,7 @@ double operator_rows(const Problem& P, const double* v, bool resid, const double
       const double c = at(i, j);
       const double Ax = -1.0 / h1 * (a1[size_t(j)] * (at(i + 1, j) - c) / h1 - a0[size_t(j)] * (c - at(i - 1, j)) / h1);
       const double Ay = -1.0 / h2 * (b[size_t(j + 1)] * (at(i, j + 1) - c) / h2 - b[size_t(j)] * (c - at(i, j - 1)) / h2);
-      const double Av = Ax + Ay;
+      const double Av = shifted ? shifted_apply(Ax + Ay, P.shift, c) : Ax + Ay;
       double o = Av;
       if (resid) {
         const double y = P.A2 + j * h2;
@@ -128,6 +135,7 @@ double operator_pass(const Problem& P, const double* v, bool resid, const double
                      const char* what) {
   if (!v) throw std::invalid_argument(std::string(what) + ": null array");
   if (P.M < 2 || P.N < 2) throw std::invalid_argument(std::string(what) + ": grid too small");
+  check_shift(P, what);
   const int64_t nx = int64_t(P.M) - 1;
   if (T <= 1) return P.h1() * P.h2() * operator_rows(P, v, resid, rhs, out, 1, nx);
   // thread t: the contiguous rows 1 + nx t / T .. nx (t + 1) / T; partials added in thread order

@@ -93,9 +93,10 @@ void assemble(const Problem& P, const Block& blk, Fields& f, int T, const double
   }
 }
 
-// Ap = A p on owned nodes (reference mat_A_local :194-213, same expression).
+// Ap = A p on owned nodes (reference mat_A_local :194-213, same expression);
+// shift σ ≠ 0: A_σ p = (Ax + Ay) + σ·p (pe/fields.hpp).
 void apply_A(const Block& blk, const double* w, const double* a, const double* b, double* Aw,
-             double h1, double h2, int T) {
+             double h1, double h2, int T, double shift) {
   const int64_t pitch = blk.pitch;
 #pragma omp parallel for schedule(static) num_threads(T) if (T > 1)
   for (int64_t li = 1; li <= blk.nx; ++li) {
@@ -104,20 +105,21 @@ void apply_A(const Block& blk, const double* w, const double* a, const double* b
       const double Ax = -1.0 / h1 *
                         (a[c + pitch] * (w[c + pitch] - w[c]) / h1 - a[c] * (w[c] - w[c - pitch]) / h1);
       const double Ay = -1.0 / h2 * (b[c + 1] * (w[c + 1] - w[c]) / h2 - b[c] * (w[c] - w[c - 1]) / h2);
-      Aw[c] = Ax + Ay;
+      Aw[c] = shift != 0.0 ? shifted_apply(Ax + Ay, shift, w[c]) : Ax + Ay;
     }
   }
 }
 
-// z = D^{-1} r (reference mat_D :219-232; D recomputed from a, b).
+// z = D^{-1} r (reference mat_D :219-232; D recomputed from a, b); shift σ ≠ 0: D_σ = D + σ.
 void apply_Dinv(const Block& blk, const double* r, const double* a, const double* b, double* z,
-                double h1, double h2, int T) {
+                double h1, double h2, int T, double shift) {
   const int64_t pitch = blk.pitch;
 #pragma omp parallel for schedule(static) num_threads(T) if (T > 1)
   for (int64_t li = 1; li <= blk.nx; ++li) {
     for (int64_t lj = 1; lj <= blk.ny; ++lj) {
       const int64_t c = blk.at(li, lj);
-      const double D = (a[c + pitch] + a[c]) / (h1 * h1) + (b[c + 1] + b[c]) / (h2 * h2);
+      double D = (a[c + pitch] + a[c]) / (h1 * h1) + (b[c + 1] + b[c]) / (h2 * h2);
+      if (shift != 0.0) D = shifted_diag(D, shift);
       z[c] = (D != 0.0) ? r[c] / D : 0.0;
     }
   }
@@ -178,6 +180,7 @@ class HaloExchanger {
 
 SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const SolveOptions& opt,
                     std::vector<double>* w_out, const UserFields& uf) {
+  check_shift(P, "cpu_pcg");
   const auto t_start = clk::now();
   SolveResult res;
   res.backend = opt.threads > 1 ? "cpu-omp" : "cpu-serial";
@@ -208,7 +211,7 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
         for (int64_t lj = 0; lj <= blk.ny + 1; ++lj)
           f.w[blk.at(li, lj)] = random_w0(blk.i0 - 1 + li, blk.j0 - 1 + lj, P.M, P.N, opt.seed, opt.init_amp);
     }
-    apply_A(blk, f.w.data(), f.a.data(), f.b.data(), f.Ap.data(), h1, h2, T);
+    apply_A(blk, f.w.data(), f.a.data(), f.b.data(), f.Ap.data(), h1, h2, T, P.shift);
     for (int64_t li = 1; li <= blk.nx; ++li)
       for (int64_t lj = 1; lj <= blk.ny; ++lj) {
         const int64_t c = blk.at(li, lj);
@@ -218,7 +221,7 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
   } else {
     f.r = f.B;
   }
-  apply_Dinv(blk, f.r.data(), f.a.data(), f.b.data(), f.z.data(), h1, h2, T);
+  apply_Dinv(blk, f.r.data(), f.a.data(), f.b.data(), f.z.data(), h1, h2, T, P.shift);
   f.p = f.z;
   // p's halo ring must come from the exchange (reference :392: p = z copies
   // whole matrices, whose halo is 0 before the first exchange).
@@ -241,7 +244,7 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
     auto t1 = clk::now();
     res.t.halo += secs(t0, t1);
 
-    apply_A(blk, f.p.data(), f.a.data(), f.b.data(), f.Ap.data(), h1, h2, T);
+    apply_A(blk, f.p.data(), f.a.data(), f.b.data(), f.Ap.data(), h1, h2, T, P.shift);
     auto t2 = clk::now();
     res.t.gpu += secs(t1, t2);
     const double* Ap = f.Ap.data();
@@ -293,7 +296,7 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
     auto t5 = clk::now();
     res.t.gpu += secs(t4, t5);
 
-    apply_Dinv(blk, f.r.data(), f.a.data(), f.b.data(), f.z.data(), h1, h2, T);
+    apply_Dinv(blk, f.r.data(), f.a.data(), f.b.data(), f.z.data(), h1, h2, T, P.shift);
     auto t6 = clk::now();
     res.t.prec += secs(t5, t6);
     double zr_new = row_sum(blk, T, [&](int64_t c) { return z[c] * r[c]; }) * h1 * h2;
@@ -348,8 +351,8 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
     }
     comm.allreduce_sum(acc, 1);
     comm.allreduce_max(mx, 2);
-    // (a user right-hand side without a user exact solution has nothing to compare with: -1)
-    const bool no_exact = uf.rhs && !uf.exact;
+    // (a user right-hand side, or a shifted operator, without a user exact solution has nothing to compare with: -1)
+    const bool no_exact = (uf.rhs || P.shift != 0.0) && !uf.exact;
     res.l2_err = no_exact ? -1.0 : std::sqrt(acc[0] * h1 * h2);
     res.max_err = no_exact ? -1.0 : mx[0];
     res.max_outside = mx[1];
@@ -371,6 +374,7 @@ SolveResult cpu_pcg_threads(const Problem& P, int ranks, DecompMode mode, const 
 
 SolveResult cpu_pcg_threads(const Problem& P, const ProcessGrid& pg, const SolveOptions& opt,
                             std::vector<double>* w_out, const UserFields& uf) {
+  check_shift(P, "cpu_pcg");  // (before any rank thread starts)
   const int ranks = pg.Px * pg.Py;
   auto group = make_thread_group(ranks);
   std::vector<SolveResult> results(ranks);

@@ -72,7 +72,16 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
   if (opt_.algo < 0 || opt_.algo > 4)
     throw std::invalid_argument("algo: 0 auto, 1 classic, 2 fused, 3 two-step, 4 three-step (got " +
                                 std::to_string(opt_.algo) + ")");
-  const bool can_fuse = opt_.variant == 0 && fused_possible(prob_, blk_);
+  // A shifted operator (Problem::shift ≠ 0) runs the classic two-kernel path
+  // on every decomposition: the single-sweep, multi-step and resident kernels
+  // do not carry the shift, and nothing below may launch one of them.
+  check_shift(prob_, "DeviceSolver");
+  const bool shifted = prob_.shift != 0.0;
+  if (shifted && opt_.algo >= 2)
+    throw std::invalid_argument(
+        "algo fused / two-step / three-step: the single-sweep kernels implement the unshifted operator only; a problem "
+        "with shift != 0 (got " + std::to_string(prob_.shift) + ") runs algo auto or classic");
+  const bool can_fuse = !shifted && opt_.variant == 0 && fused_possible(prob_, blk_);
   if (opt_.algo >= 2 && !can_fuse)
     throw std::invalid_argument("single-sweep algorithm needs variant 0 and >= 2 rows/columns per split block");
   fused_ = opt_.algo >= 2 || (opt_.algo == 0 && can_fuse);
@@ -382,7 +391,7 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
   if (!fused_ && k.order > 1) k.order = 0;
   if (sstep_) k.order = 0;
   k.ti = (fused_ && ti_env < 0) ? 1 << 20 : ti;  // bands mode: long items → general kernel
-  int per_cu = fused_ ? dev::resident_blocks_S(k, 2) : dev::resident_blocks_classic(opt_.variant);
+  int per_cu = fused_ ? dev::resident_blocks_S(k, 2) : dev::resident_blocks_classic(opt_.variant, prob_.shift != 0.0);
   if (per_cu <= 0) per_cu = 4;
   int wave_cap = cus * per_cu * dev::kWPB;
   // PE_TI=-1 (single-sweep): "bands" — one item per resident wave, the rows
@@ -435,6 +444,13 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
   k.D_out = (k.inv_eps + k.inv_eps) / k.h1sq + (k.inv_eps + k.inv_eps) / k.h2sq;
   k.dinv_in = 1.0 / ((1.0 + 1.0) * k.ih1sq + (1.0 + 1.0) * k.ih2sq);
   k.dinv_out = 1.0 / ((k.inv_eps + k.inv_eps) * k.ih1sq + (k.inv_eps + k.inv_eps) * k.ih2sq);
+  k.shift = prob_.shift;
+  if (k.shift != 0.0) {  // the diagonal of A + σI in the two uniform classes (pe/fields.hpp; the band adds σ in cset)
+    k.D_in = shifted_diag(k.D_in, k.shift);
+    k.D_out = shifted_diag(k.D_out, k.shift);
+    k.dinv_in = 1.0 / shifted_diag((1.0 + 1.0) * k.ih1sq + (1.0 + 1.0) * k.ih2sq, k.shift);
+    k.dinv_out = 1.0 / shifted_diag((k.inv_eps + k.inv_eps) * k.ih1sq + (k.inv_eps + k.inv_eps) * k.ih2sq, k.shift);
+  }
   mark("buffers");
   build_tables(rows_hi, cols_hi);
   const bool has[4] = {blk_.has(LEFT), blk_.has(RIGHT), blk_.has(DOWN), blk_.has(UP)};
@@ -1604,8 +1620,8 @@ SolveResult DeviceSolver::solve() {
   }
   res.zr = hs.rz_cur;
   if (opt_.compute_error) {
-    // (a user right-hand side without a user exact solution has nothing to compare with: -1)
-    const bool no_exact = rhs_dev_ && !exact_dev_;
+    // (a user right-hand side, or a shifted operator, without a user exact solution has nothing to compare with: -1)
+    const bool no_exact = (rhs_dev_ || prob_.shift != 0.0) && !exact_dev_;
     res.l2_err = no_exact ? -1.0 : std::sqrt(hs.err[0] * prob_.h1() * prob_.h2());
     res.max_err = no_exact ? -1.0 : hs.err[1];
     res.max_outside = hs.err[2];
@@ -1922,7 +1938,7 @@ SolveResult device_solve_group(const Problem& P, const ProcessGrid& pg, const So
   res.last_diff = hs.last_diff;
   res.zr = hs.rz_cur;
   if (opt.compute_error) {
-    const bool no_exact = (uf.rhs || df.rhs) && !(uf.exact || df.exact);
+    const bool no_exact = (uf.rhs || df.rhs || P.shift != 0.0) && !(uf.exact || df.exact);
     res.l2_err = no_exact ? -1.0 : std::sqrt(hs.err[0] * P.h1() * P.h2());
     res.max_err = no_exact ? -1.0 : hs.err[1];
     res.max_outside = hs.err[2];

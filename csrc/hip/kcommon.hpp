@@ -9,6 +9,7 @@
 
 #include "kernels.hpp"
 #include "pe/decomp.hpp"
+#include "pe/fields.hpp"  // shifted_apply / shifted_diag: the shifted operator's expression trees
 #include "pe/problem.hpp"
 
 namespace pe {
@@ -58,11 +59,13 @@ __device__ __forceinline__ double coefB(const KParams& k, int64_t q, double half
 
 // Coefficients of node (q, lj): a(q), a(q+1), b(q, lj), b(q, lj+1), and the
 // Jacobi diagonal (EXACT: D, used as r / D; fast: 1/D, used as r * dinv).
+// SHIFT (Problem::shift = σ ≠ 0, kernels.hip only): the diagonal of A + σI —
+// the host sets D_in / D_out / dinv_in / dinv_out with σ, the band adds it here.
 struct CS {
   double a0, a1, b0, b1, d;
 };
 
-template <bool EXACT>
+template <bool EXACT, bool SHIFT = false>
 __device__ __forceinline__ CS cset(const KParams& k, const int* rc, int64_t q, int64_t lj, const TV& t) {
   CS c;
   const int in_lo = cload(rc), in_hi = cload(rc + 1), out_lo = cload(rc + 2), out_hi = cload(rc + 3);
@@ -78,14 +81,17 @@ __device__ __forceinline__ CS cset(const KParams& k, const int* rc, int64_t q, i
     c.b0 = coefB(k, q, t.hB);
     c.b1 = coefB(k, q, t.hB1);
     // D = (a_{i+1} + a_i)/h1² + (b_{j+1} + b_j)/h2²  (reference mat_D, same order)
-    if constexpr (EXACT) c.d = (c.a1 + c.a0) / k.h1sq + (c.b1 + c.b0) / k.h2sq;
+    if constexpr (SHIFT) {
+      if constexpr (EXACT) c.d = shifted_diag((c.a1 + c.a0) / k.h1sq + (c.b1 + c.b0) / k.h2sq, k.shift);
+      else c.d = 1.0 / shifted_diag((c.a1 + c.a0) * k.ih1sq + (c.b1 + c.b0) * k.ih2sq, k.shift);
+    } else if constexpr (EXACT) c.d = (c.a1 + c.a0) / k.h1sq + (c.b1 + c.b0) / k.h2sq;
     else c.d = 1.0 / ((c.a1 + c.a0) * k.ih1sq + (c.b1 + c.b0) * k.ih2sq);
   }
   return c;
 }
-template <bool EXACT>
+template <bool EXACT, bool SHIFT = false>
 __device__ __forceinline__ CS cset_mem(const KParams& k, int64_t q, int64_t lj) {
-  return cset<EXACT>(k, k.rowcls + (q + 1) * 4, q, lj, tv_at(k, lj));
+  return cset<EXACT, SHIFT>(k, k.rowcls + (q + 1) * 4, q, lj, tv_at(k, lj));
 }
 
 template <bool EXACT>
@@ -94,17 +100,21 @@ __device__ __forceinline__ double zval(const CS& c, double r) {
   else return r * c.d;
 }
 
-template <bool EXACT>
+// SHIFT: A_σ p = A p + σ·p₀ (pe/fields.hpp shifted_apply; kernels.hip only — built without contraction).
+template <bool EXACT, bool SHIFT = false>
 __device__ __forceinline__ double stencil(const KParams& k, const CS& c, double pm, double p0, double pn, double pl,
                                           double pr) {
+  double Ap;
   if constexpr (EXACT) {
     // Reference apply_A (poisson_mpi_cuda2.cu:526-535), same expression tree.
     const double Ax = k.nih1 * (c.a1 * (pn - p0) / k.h1 - c.a0 * (p0 - pm) / k.h1);
     const double Ay = k.nih2 * (c.b1 * (pr - p0) / k.h2 - c.b0 * (p0 - pl) / k.h2);
-    return Ax + Ay;
+    Ap = Ax + Ay;
   } else {
-    return (c.a0 * (p0 - pm) - c.a1 * (pn - p0)) * k.ih1sq + (c.b0 * (p0 - pl) - c.b1 * (pr - p0)) * k.ih2sq;
+    Ap = (c.a0 * (p0 - pm) - c.a1 * (pn - p0)) * k.ih1sq + (c.b0 * (p0 - pl) - c.b1 * (pr - p0)) * k.ih2sq;
   }
+  if constexpr (SHIFT) return shifted_apply(Ap, k.shift, p0);
+  else return Ap;
 }
 
 __device__ __forceinline__ bool row_valid(const KParams& k, int64_t q) {
@@ -364,9 +374,9 @@ __device__ __forceinline__ void reduce_partials_nm(const double* partial, double
 }
 
 // One p_k value at a single node (strip-edge columns, prologue only).
-template <bool EXACT>
+template <bool EXACT, bool SHIFT = false>
 __device__ __forceinline__ double p_point(const KParams& k, int64_t q, int64_t lj, double beta, const double* pold) {
-  return zval<EXACT>(cset_mem<EXACT>(k, q, lj), load_r(k, q, lj)) + beta * pold[q * k.pitch + lj];
+  return zval<EXACT>(cset_mem<EXACT, SHIFT>(k, q, lj), load_r(k, q, lj)) + beta * pold[q * k.pitch + lj];
 }
 
 // Unconditional 16-byte load (address already clamped in range): a

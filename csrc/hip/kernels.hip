@@ -52,7 +52,7 @@ struct SegData {
 // F: p_k = D⁻¹ r_k + β p_{k-1} on owned nodes and the halo ring, then
 //    S_den = Σ (A p_k)·p_k and S_pp = Σ p_k·p_k over owned nodes.
 // ---------------------------------------------------------------------------
-template <bool EXACT>
+template <bool EXACT, bool SHIFT = false>
 __global__ __launch_bounds__(TJ) void kF(KParams k, int par) {
   DevState* st = k.st;
   if (st->done) return;
@@ -97,11 +97,11 @@ __global__ __launch_bounds__(TJ) void kF(KParams k, int par) {
         const int q = s0 + t;
         const int jl = j0 - 1, jr = j0 + SW;
         if (valid_node(k, q, jl)) {
-          d.hL = p_point<EXACT>(k, q, jl, beta, pold);
+          d.hL = p_point<EXACT, SHIFT>(k, q, jl, beta, pold);
           if (jl == 0) pnew[q * pitch] = d.hL;  // rank-halo column: ours to write
         }
         if (jr <= ny + 1 && valid_node(k, q, jr)) {
-          d.hR = p_point<EXACT>(k, q, jr, beta, pold);
+          d.hR = p_point<EXACT, SHIFT>(k, q, jr, beta, pold);
           if (jr == ny + 1) pnew[q * pitch + jr] = d.hR;
         }
       }
@@ -121,8 +121,8 @@ __global__ __launch_bounds__(TJ) void kF(KParams k, int par) {
         s1 = cset_fast<EXACT>(k, rc, c1);
       } else {
         const int* rcp = k.rowcls + (q + 1) * 4;
-        s0 = cset<EXACT>(k, rcp, q, c0, tv_at(k, ca));
-        s1 = cset<EXACT>(k, rcp, q, c1, tv_at(k, ca + 1));
+        s0 = cset<EXACT, SHIFT>(k, rcp, q, c0, tv_at(k, ca));
+        s1 = cset<EXACT, SHIFT>(k, rcp, q, c1, tv_at(k, ca + 1));
       }
       const bool e0 = rv && (rin ? live0 : own0), e1 = rv && (rin ? live1 : own1);
       v0 = e0 ? zval<EXACT>(s0, r0) + beta * po.x : 0.0;
@@ -187,11 +187,11 @@ __global__ __launch_bounds__(TJ) void kF(KParams k, int par) {
           x1 = cset_fast<EXACT>(k, ci, c1);
         } else {
           const int* rcp = k.rowcls + (i + 1) * 4;
-          x0 = cset<EXACT>(k, rcp, i, c0, tv_at(k, ca));
-          x1 = cset<EXACT>(k, rcp, i, c1, tv_at(k, ca + 1));
+          x0 = cset<EXACT, SHIFT>(k, rcp, i, c0, tv_at(k, ca));
+          x1 = cset<EXACT, SHIFT>(k, rcp, i, c1, tv_at(k, ca + 1));
         }
-        const double Ap0 = stencil<EXACT>(k, x0, pm0, p00, pn0, pl0, p01);
-        const double Ap1 = stencil<EXACT>(k, x1, pm1, p01, pn1, p00, pr1);
+        const double Ap0 = stencil<EXACT, SHIFT>(k, x0, pm0, p00, pn0, pl0, p01);
+        const double Ap1 = stencil<EXACT, SHIFT>(k, x1, pm1, p01, pn1, p00, pr1);
         if (own0) {
           sden += Ap0 * p00;
           spp += p00 * p00;
@@ -234,7 +234,7 @@ __global__ __launch_bounds__(TJ) void kF(KParams k, int par) {
 // ---------------------------------------------------------------------------
 // G: α = rz/den, stop test, w += α p, r -= α A p, S_zr = Σ (D⁻¹r)·r.
 // ---------------------------------------------------------------------------
-template <bool EXACT>
+template <bool EXACT, bool SHIFT = false>
 __global__ __launch_bounds__(TJ) void kG(KParams k, int par) {
   DevState* st = k.st;
   if (st->done) return;
@@ -329,11 +329,11 @@ __global__ __launch_bounds__(TJ) void kG(KParams k, int par) {
           x1 = cset_fast<EXACT>(k, ci, c1);
         } else {
           const int* rcp = k.rowcls + (i + 1) * 4;
-          x0 = cset<EXACT>(k, rcp, i, c0, tv_at(k, ca));
-          x1 = cset<EXACT>(k, rcp, i, c1, tv_at(k, ca + 1));
+          x0 = cset<EXACT, SHIFT>(k, rcp, i, c0, tv_at(k, ca));
+          x1 = cset<EXACT, SHIFT>(k, rcp, i, c1, tv_at(k, ca + 1));
         }
-        const double Ap0 = stencil<EXACT>(k, x0, pm0, pB.x, pN.x, pl0, pB.y);
-        const double Ap1 = stencil<EXACT>(k, x1, pm1, pB.y, pN.y, pB.x, pr1);
+        const double Ap0 = stencil<EXACT, SHIFT>(k, x0, pm0, pB.x, pN.x, pl0, pB.y);
+        const double Ap1 = stencil<EXACT, SHIFT>(k, x1, pm1, pB.y, pN.y, pB.x, pr1);
         const double wn0 = wC.x + alpha * pB.x, wn1 = wC.y + alpha * pB.y;
         const double rn0 = rC.x - alpha * Ap0, rn1 = rC.y - alpha * Ap1;
         if (own0) szr += zval<EXACT>(x0, rn0) * rn0;
@@ -390,7 +390,7 @@ __global__ __launch_bounds__(TJ) void kG(KParams k, int par) {
 // ---------------------------------------------------------------------------
 // Init: r⁰ = B - A w⁰ (w⁰ = 0 or a global-index hash), S_zr⁰ = Σ (D⁻¹r⁰)·r⁰.
 // ---------------------------------------------------------------------------
-template <bool EXACT>
+template <bool EXACT, bool SHIFT = false>
 __global__ __launch_bounds__(TJ) void kInit(KParams k, int init_random, unsigned long long seed, double amp) {
   __shared__ double sm[8];
   __shared__ int sflag;
@@ -401,12 +401,12 @@ __global__ __launch_bounds__(TJ) void kInit(KParams k, int init_random, unsigned
     const int64_t li = idx / k.ny + 1, lj = idx % k.ny + 1;
     const int64_t gi = k.gi0 + li, gj = k.gj0 + lj;
     const double x = k.A1 + gi * k.h1, y = k.A2 + gj * k.h2;
-    const CS c = cset_mem<EXACT>(k, li, lj);
+    const CS c = cset_mem<EXACT, SHIFT>(k, li, lj);
     double rr = in_ellipse(x, y, k.cx, k.cy) ? k.F : 0.0;
     const int64_t at = li * k.pitch + lj;
     if (init_random) {
       const double w0 = random_w0(gi, gj, k.M, k.N, seed, amp);
-      const double Aw = stencil<EXACT>(k, c, random_w0(gi - 1, gj, k.M, k.N, seed, amp), w0,
+      const double Aw = stencil<EXACT, SHIFT>(k, c, random_w0(gi - 1, gj, k.M, k.N, seed, amp), w0,
                                        random_w0(gi + 1, gj, k.M, k.N, seed, amp),
                                        random_w0(gi, gj - 1, k.M, k.N, seed, amp),
                                        random_w0(gi, gj + 1, k.M, k.N, seed, amp));
@@ -443,7 +443,7 @@ __global__ __launch_bounds__(TJ) void kInit(KParams k, int init_random, unsigned
 // 0 on the box boundary; null: kInit's zero / hash start).  Same stores (w
 // with wpitch, r with pitch into the live layout — k.r is the classic r or
 // the r-plane of x[0] behind its xorg), same sum protocol.
-template <bool EXACT>
+template <bool EXACT, bool SHIFT = false>
 __global__ __launch_bounds__(TJ) void kInitField(KParams k, const double* __restrict__ Bp,
                                                  const double* __restrict__ W0, int init_random,
                                                  unsigned long long seed, double amp) {
@@ -456,18 +456,18 @@ __global__ __launch_bounds__(TJ) void kInitField(KParams k, const double* __rest
     const int64_t li = idx / k.ny + 1, lj = idx % k.ny + 1;
     const int64_t gi = k.gi0 + li, gj = k.gj0 + lj;
     const double x = k.A1 + gi * k.h1, y = k.A2 + gj * k.h2;
-    const CS c = cset_mem<EXACT>(k, li, lj);
+    const CS c = cset_mem<EXACT, SHIFT>(k, li, lj);
     double rr = in_ellipse(x, y, k.cx, k.cy) ? (Bp ? Bp[idx] : k.F) : 0.0;
     const int64_t at = li * k.pitch + lj;
     if (W0) {
       const int64_t q = li * wc + lj;
       const double w0 = W0[q];
-      const double Aw = stencil<EXACT>(k, c, W0[q - wc], w0, W0[q + wc], W0[q - 1], W0[q + 1]);
+      const double Aw = stencil<EXACT, SHIFT>(k, c, W0[q - wc], w0, W0[q + wc], W0[q - 1], W0[q + 1]);
       rr = rr - Aw;
       k.w[li * k.wpitch + lj] = w0;
     } else if (init_random) {
       const double w0 = random_w0(gi, gj, k.M, k.N, seed, amp);
-      const double Aw = stencil<EXACT>(k, c, random_w0(gi - 1, gj, k.M, k.N, seed, amp), w0,
+      const double Aw = stencil<EXACT, SHIFT>(k, c, random_w0(gi - 1, gj, k.M, k.N, seed, amp), w0,
                                        random_w0(gi + 1, gj, k.M, k.N, seed, amp),
                                        random_w0(gi, gj - 1, k.M, k.N, seed, amp),
                                        random_w0(gi, gj + 1, k.M, k.N, seed, amp));
@@ -823,7 +823,7 @@ __device__ __forceinline__ double field_in_row(const T* col, int64_t si, int64_t
   const double v = double(col[(gi - 1) * si]);
   return col_ok ? v : 0.0;
 }
-template <typename T, bool RESID, bool STORE>
+template <typename T, bool RESID, bool STORE, bool SHIFT = false>
 __global__ __launch_bounds__(TJ) void kApplyField(KParams k, const T* __restrict__ g, int64_t si, int64_t sj,
                                                   const double* __restrict__ Bp, int trows, int64_t ctiles,
                                                   int64_t ntiles, double* __restrict__ dst, int64_t dsi, int64_t dsj,
@@ -870,8 +870,8 @@ __global__ __launch_bounds__(TJ) void kApplyField(KParams k, const T* __restrict
       for (int u = 0; u < kApplyU; ++u) {
         const int64_t q = li + u;
         if (q <= li1) {
-          const CS c = cset<true>(k, k.rowcls + (q + 1) * 4, q, lj, tv);
-          const double Av = stencil<true>(k, c, wm, wc, dn[u], dl[u], dr[u]);
+          const CS c = cset<true, SHIFT>(k, k.rowcls + (q + 1) * 4, q, lj, tv);
+          const double Av = stencil<true, SHIFT>(k, c, wm, wc, dn[u], dl[u], dr[u]);
           double o = Av;
           if constexpr (RESID) {
             const double x = k.A1 + (k.gi0 + q) * k.h1;
@@ -944,25 +944,26 @@ __global__ void kGroupReduce(double* const* bufs, int nranks, int n, int is_max)
 }
 
 // Test op: Ap = A p on owned nodes (p halo must be valid).
-template <bool EXACT>
+template <bool EXACT, bool SHIFT = false>
 __global__ void kApplyA(KParams k, const double* p, double* Ap) {
   const int64_t n = k.nx * k.ny;
   for (int64_t idx = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; idx < n;
        idx += int64_t(gridDim.x) * blockDim.x) {
     const int64_t li = idx / k.ny + 1, lj = idx % k.ny + 1;
     const int64_t c = li * k.pitch + lj;
-    const CS cs = cset_mem<EXACT>(k, li, lj);
-    Ap[c] = stencil<EXACT>(k, cs, p[c - k.pitch], p[c], p[c + k.pitch], p[c - 1], p[c + 1]);
+    const CS cs = cset_mem<EXACT, SHIFT>(k, li, lj);
+    Ap[c] = stencil<EXACT, SHIFT>(k, cs, p[c - k.pitch], p[c], p[c + k.pitch], p[c - 1], p[c + 1]);
   }
 }
 
 // Test op: a_ij, b_ij, D_ij through the class table (checks the classification).
+template <bool SHIFT = false>
 __global__ void kCoef(KParams k, double* a, double* b, double* D) {
   const int64_t n = (k.nx + 2) * (k.ny + 2);
   for (int64_t idx = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; idx < n;
        idx += int64_t(gridDim.x) * blockDim.x) {
     const int64_t li = idx / (k.ny + 2), lj = idx % (k.ny + 2);
-    const CS cs = cset_mem<true>(k, li, lj);
+    const CS cs = cset_mem<true, SHIFT>(k, li, lj);
     const int64_t c = li * k.pitch + lj;
     a[c] = cs.a0;
     b[c] = cs.b0;
@@ -986,9 +987,15 @@ void launch_delay(double us, hipStream_t s) {
   hipLaunchKernelGGL(kDelay, dim3(1), dim3(64), 0, s, ticks);
 }
 
-int resident_blocks_classic(int variant) {
+int resident_blocks_classic(int variant, bool shift) {
   int n = 0, m = 0;
-  if (variant == 1) {
+  if (shift && variant == 1) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kF<true, true>, TJ, 0) != hipSuccess) n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&m, kG<true, true>, TJ, 0) != hipSuccess) m = 0;
+  } else if (shift) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kF<false, true>, TJ, 0) != hipSuccess) n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&m, kG<false, true>, TJ, 0) != hipSuccess) m = 0;
+  } else if (variant == 1) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kF<true>, TJ, 0) != hipSuccess) n = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&m, kG<true>, TJ, 0) != hipSuccess) m = 0;
   } else {
@@ -1006,14 +1013,29 @@ static unsigned flat_blocks(const KParams& k) {
   return unsigned(b);
 }
 
+// Problem::shift ≠ 0 → the SHIFT instantiations; each wrapper decides here, once.
+static bool shifted(const KParams& k) { return k.shift != 0.0; }
+
 void launch_init(const KParams& k, int init_random, unsigned long long seed, double amp, int variant,
                  hipStream_t s) {
+  if (shifted(k)) {
+    if (variant == 1) hipLaunchKernelGGL((kInit<true, true>), dim3(flat_blocks(k)), dim3(TJ), 0, s, k, init_random, seed, amp);
+    else hipLaunchKernelGGL((kInit<false, true>), dim3(flat_blocks(k)), dim3(TJ), 0, s, k, init_random, seed, amp);
+    return;
+  }
   if (variant == 1) hipLaunchKernelGGL(kInit<true>, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, init_random, seed, amp);
   else hipLaunchKernelGGL(kInit<false>, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, init_random, seed, amp);
 }
 
 void launch_init_field(const KParams& k, const double* rhs, const double* w0, int init_random,
                        unsigned long long seed, double amp, int variant, hipStream_t s) {
+  if (shifted(k)) {
+    if (variant == 1)
+      hipLaunchKernelGGL((kInitField<true, true>), dim3(flat_blocks(k)), dim3(TJ), 0, s, k, rhs, w0, init_random, seed, amp);
+    else
+      hipLaunchKernelGGL((kInitField<false, true>), dim3(flat_blocks(k)), dim3(TJ), 0, s, k, rhs, w0, init_random, seed, amp);
+    return;
+  }
   if (variant == 1)
     hipLaunchKernelGGL(kInitField<true>, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, rhs, w0, init_random, seed, amp);
   else
@@ -1021,11 +1043,21 @@ void launch_init_field(const KParams& k, const double* rhs, const double* w0, in
 }
 
 void launch_F(const KParams& k, int par, int variant, hipStream_t s) {
+  if (shifted(k)) {
+    if (variant == 1) hipLaunchKernelGGL((kF<true, true>), dim3(k.nblocks), dim3(TJ), 0, s, k, par);
+    else hipLaunchKernelGGL((kF<false, true>), dim3(k.nblocks), dim3(TJ), 0, s, k, par);
+    return;
+  }
   if (variant == 1) hipLaunchKernelGGL(kF<true>, dim3(k.nblocks), dim3(TJ), 0, s, k, par);
   else hipLaunchKernelGGL(kF<false>, dim3(k.nblocks), dim3(TJ), 0, s, k, par);
 }
 
 void launch_G(const KParams& k, int par, int variant, hipStream_t s) {
+  if (shifted(k)) {
+    if (variant == 1) hipLaunchKernelGGL((kG<true, true>), dim3(k.nblocks), dim3(TJ), 0, s, k, par);
+    else hipLaunchKernelGGL((kG<false, true>), dim3(k.nblocks), dim3(TJ), 0, s, k, par);
+    return;
+  }
   if (variant == 1) hipLaunchKernelGGL(kG<true>, dim3(k.nblocks), dim3(TJ), 0, s, k, par);
   else hipLaunchKernelGGL(kG<false>, dim3(k.nblocks), dim3(TJ), 0, s, k, par);
 }
@@ -1109,7 +1141,7 @@ void launch_grad_field(const KParams& k, const double* plane, int64_t pitch, dou
                        int64_t(0));
 }
 namespace {
-template <typename T, bool RESID>
+template <typename T, bool RESID, bool SHIFT>
 void apply_field_launch(const KParams& k, const T* g, int64_t si, int64_t sj, const double* rhs, double* dst,
                         int64_t dsi, int64_t dsj, int64_t off_i, int64_t off_j, hipStream_t s) {
   // launch_grad_field's tiling: ≈ 2048 tiles where the block has them, 8 .. 64 rows each, ≤ 4096 blocks
@@ -1119,10 +1151,10 @@ void apply_field_launch(const KParams& k, const T* g, int64_t si, int64_t sj, co
   const int64_t ntiles = ctiles * ((k.nx + trows - 1) / trows);
   const dim3 grid(unsigned(std::min<int64_t>(ntiles, 4096))), block(TJ);
   if (dst)
-    hipLaunchKernelGGL((kApplyField<T, RESID, true>), grid, block, 0, s, k, g, si, sj, rhs, trows, ctiles, ntiles, dst,
+    hipLaunchKernelGGL((kApplyField<T, RESID, true, SHIFT>), grid, block, 0, s, k, g, si, sj, rhs, trows, ctiles, ntiles, dst,
                        dsi, dsj, off_i, off_j);
   else
-    hipLaunchKernelGGL((kApplyField<T, RESID, false>), grid, block, 0, s, k, g, si, sj, rhs, trows, ctiles, ntiles,
+    hipLaunchKernelGGL((kApplyField<T, RESID, false, SHIFT>), grid, block, 0, s, k, g, si, sj, rhs, trows, ctiles, ntiles,
                        static_cast<double*>(nullptr), int64_t(0), int64_t(0), int64_t(0), int64_t(0));
 }
 }  // namespace
@@ -1131,10 +1163,17 @@ void launch_apply_field(const KParams& k, const void* g, bool f32, int64_t si, i
                         hipStream_t s) {
   const float* gf = static_cast<const float*>(g);
   const double* gd = static_cast<const double*>(g);
-  if (f32 && resid) apply_field_launch<float, true>(k, gf, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
-  else if (f32) apply_field_launch<float, false>(k, gf, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
-  else if (resid) apply_field_launch<double, true>(k, gd, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
-  else apply_field_launch<double, false>(k, gd, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
+  if (shifted(k)) {
+    if (f32 && resid) apply_field_launch<float, true, true>(k, gf, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
+    else if (f32) apply_field_launch<float, false, true>(k, gf, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
+    else if (resid) apply_field_launch<double, true, true>(k, gd, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
+    else apply_field_launch<double, false, true>(k, gd, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
+    return;
+  }
+  if (f32 && resid) apply_field_launch<float, true, false>(k, gf, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
+  else if (f32) apply_field_launch<float, false, false>(k, gf, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
+  else if (resid) apply_field_launch<double, true, false>(k, gd, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
+  else apply_field_launch<double, false, false>(k, gd, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
 }
 void launch_zero_p(const KParams& k, int b, hipStream_t s) {
   hipLaunchKernelGGL(kZeroP, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, b);
@@ -1149,11 +1188,13 @@ void launch_group_reduce(double* const* bufs, int nranks, int n, int is_max, hip
 }
 
 void launch_apply_A(const KParams& k, const double* p, double* Ap, hipStream_t s) {
-  hipLaunchKernelGGL(kApplyA<false>, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, p, Ap);
+  if (shifted(k)) hipLaunchKernelGGL((kApplyA<false, true>), dim3(flat_blocks(k)), dim3(TJ), 0, s, k, p, Ap);
+  else hipLaunchKernelGGL(kApplyA<false>, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, p, Ap);
 }
 
 void launch_coef(const KParams& k, double* a, double* b, double* D, hipStream_t s) {
-  hipLaunchKernelGGL(kCoef, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, a, b, D);
+  if (shifted(k)) hipLaunchKernelGGL(kCoef<true>, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, a, b, D);
+  else hipLaunchKernelGGL(kCoef<false>, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, a, b, D);
 }
 
 }  // namespace dev

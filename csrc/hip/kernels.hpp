@@ -247,6 +247,11 @@ struct KParams {
   // three-step sweep: stage each wave's first item's first rows into LDS at
   // kernel entry (fused3.hip stage_first3; PE_STAGE=0: off)
   int stage;
+  // Problem::shift σ of A + σI (classic layout and the operator pass only: the
+  // launch wrappers of kernels.hip pick their SHIFT instantiations when it is
+  // non-zero; D_in / D_out / dinv_in / dinv_out then hold the shifted diagonal).
+  // Last member: every other kernarg offset stays where it was.
+  double shift;
 };
 // KParams::mlimit of the three-step replay launch (DevState::fixj)
 constexpr int kReplay3 = -2;
@@ -406,7 +411,8 @@ void launch_S3(const KParams& k, int par, hipStream_t s);
 int resident_blocks_S3();
 constexpr int sweep_sums(int steps) { return steps >= 3 ? kNS3 : steps == 2 ? kNS2 : 7; }
 // (k.ti / k.order select the kernel variant: set them first)
-int resident_blocks_classic(int variant);
+// (shift: the SHIFT instantiations of kF / kG — Problem::shift ≠ 0)
+int resident_blocks_classic(int variant, bool shift = false);
 
 }  // namespace dev
 }  // namespace pe

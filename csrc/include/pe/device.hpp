@@ -286,6 +286,9 @@ class DeviceSolver {
 
   // Checkpoint / resume of the full device state of this rank (raw fields,
   // halo buffers, scalar block, iteration parity).  Synchronizes the stream.
+  // The format holds no problem data: a resumed solve needs the same
+  // Problem::shift again (as it needs the same rhs), or it iterates on
+  // another operator from this one's state.
   void save_checkpoint(const std::string& path);
   void load_checkpoint(const std::string& path);
 

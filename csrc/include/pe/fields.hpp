@@ -72,8 +72,23 @@ GradStats gradient_field(const Problem& prob, const double* w, double* gx, doubl
 // out = A v over the global interior (M−1) × (N−1); v is 0 on the box boundary.
 // Every interior node, inside or outside the ellipse (the fictitious-domain
 // system has unknowns everywhere).  Returns h1·h2·Σ v·(A v).  `out` may be
-// null: the sum only.
+// null: the sum only.  With prob.shift = σ > 0 both functions take A_σ (below)
+// for A: out = A_σ v and h1·h2·Σ v·(A_σ v), out = B − A_σ w and h1·h2·Σ out².
 double apply_operator(const Problem& prob, const double* v, double* out, int threads = 1);
+// The shifted operator A_σ = A + σI (Problem::shift = σ > 0; −Δu + σu = f) —
+// the two expression trees every backend uses, host and device:
+//   A_σ p = (Ax + Ay) + σ·p     the unshifted tree, then one multiply and one add;
+//   D_σ   = D + σ               D = (a₁+a₀)/h1² + (b₁+b₀)/h2² (the fast device
+//                               variant: its own sum of products), z = r / D_σ.
+// Nothing is contracted into an FMA (host: no FMA target; device: kernels.hip
+// is built with -ffp-contract=off).  The system holds at every interior node
+// of the box, inside and outside the ellipse; B and its mask are unchanged.
+// σ = 0 never comes here: callers keep the unshifted expression (not x + 0·p).
+PE_HD double shifted_apply(double Av, double sigma, double p) { return Av + sigma * p; }
+PE_HD double shifted_diag(double D, double sigma) { return D + sigma; }
+// std::invalid_argument unless prob.shift is finite and ≥ 0 (a negative shift
+// makes the system indefinite).  Every backend calls it before any work.
+void check_shift(const Problem& prob, const char* who);
 // out = B − A w, B = rhs (null: F) at nodes inside the ellipse, 0 elsewhere
 // (assemble()'s mask).  Returns h1·h2·Σ out².  `out` may be null.
 double residual_field(const Problem& prob, const double* w, const double* rhs, double* out, int threads = 1);

@@ -42,6 +42,9 @@ struct Problem {
   double tol = 1e-6;
   int64_t max_iter = -1;  // <0 → (M-1)(N-1)
   Norm norm = Norm::Weighted;
+  // Constant shift σ ≥ 0 of the operator: (A + σI) w = B, the discrete
+  // −Δu + σu = f (pe/fields.hpp).  0.0: −Δu = f, the unshifted code bit for bit.
+  double shift = 0.0;
 
   double h1() const { return (B1 - A1) / M; }
   double h2() const { return (B2 - A2) / N; }

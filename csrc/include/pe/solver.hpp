@@ -124,6 +124,9 @@ struct SolveResult {
 // `fields`: the user right-hand side / initial guess as GLOBAL interior arrays
 // (pe/fields.hpp; every rank passes the same arrays and takes its slice).  With
 // a user rhs the analytic solution does not apply: l2_err = max_err = -1.
+// prob.shift = σ > 0 solves (A + σI) w = B with the preconditioner D + σ
+// (pe/fields.hpp); the analytic error is then -1 too unless fields.exact is
+// given.  std::invalid_argument for a negative or non-finite shift.
 SolveResult cpu_pcg(const Problem& prob, const Block& blk, HostComm& comm,
                     const SolveOptions& opt, std::vector<double>* w_out = nullptr,
                     const UserFields& fields = UserFields());

@@ -38,8 +38,16 @@ h1 h2 Σ_D |∇w|² and max_D |∇w| on a line of their own after the result lin
 of its own — the stop test is the step size, so this is where to look for
 what the iterate still misses.
 
+``--shift S`` (finite, >= 0) solves the shifted problem −Δu + S·u = f,
+(A + S·I) w = B — an implicit heat step with S = 1/dt, say.  The analytic
+solution does not apply: the error line reads ``n/a`` unless ``--exact`` is
+given, and ``--json`` carries ``"shift"``.  The device backends run the classic
+two-kernel iteration (``--algo auto`` or ``classic``):
+
+    python -m poisson_ellipse_openmp_mpi_cuda_amd.cli --shift 40 --rhs f.npy --w0 u.npy --dump u1.npy 400 600
+
 Checkpoints hold the iteration state, not the fields: ``--resume`` needs the
-same ``--rhs`` (and ``--exact``) again, and ignores ``--w0``.
+same ``--rhs`` (and ``--exact``) and the same ``--shift`` again, and ignores ``--w0``.
 """
 
 from __future__ import annotations
@@ -81,6 +89,10 @@ def build_parser():
                     help="user exact solution: float64 (M-1, N-1) array the L2 / max error in D is measured against "
                          "(in place of the analytic solution; values outside the ellipse are ignored); never enters "
                          "the solve")
+    ap.add_argument("--shift", type=float, default=0.0, metavar="S",
+                    help="constant shift S >= 0 of the operator: solve -Laplace(u) + S u = f, (A + S I) w = B (default 0: "
+                         "the unshifted solve); the L2 / max error is then reported only with --exact; device backends "
+                         "run --algo auto / classic; a resumed solve (--resume) needs the same --shift again")
     ap.add_argument("--tol", type=float, default=1e-6)
     ap.add_argument("--max-iter", type=int, default=-1)
     ap.add_argument("--norm", choices=("weighted", "unweighted"), default="weighted")
@@ -117,8 +129,10 @@ def main(argv=None) -> int:
     prob.tol = a.tol
     prob.max_iter = a.max_iter
     prob.norm = a.norm
+    prob.shift = a.shift
     want_w = bool(a.dump or a.pgm or a.dump_resid)
     try:
+        prob.check_shift()
         rhs = None if a.rhs is None else user_field("--rhs", np.load(a.rhs, allow_pickle=False), prob)
         w0 = None if a.w0 is None else user_field("--w0", np.load(a.w0, allow_pickle=False), prob)
         exact = None if a.exact is None else user_field("--exact", np.load(a.exact, allow_pickle=False), prob)
@@ -134,10 +148,12 @@ def main(argv=None) -> int:
         return 0
     if not a.quiet:
         print(legacy_lines(rep, a.tol))
-        if rhs is None or exact is not None:
+        if (rhs is None and prob.shift == 0.0) or exact is not None:
             err = f"L2 error in D ~ {rep.l2_err:.6e} | max error in D ~ {rep.max_err:.6e}"
-        else:
+        elif rhs is not None:
             err = "L2 error in D ~ n/a (user right-hand side)"
+        else:
+            err = "L2 error in D ~ n/a (shifted operator)"
         print(f"   Process grid {rep.Px}x{rep.Py} | iters/s ~ {rep.iters_per_s:.1f} | {err}")
     if a.grad_stats:
         print(f"   Integral of w in D ~ {rep.integral:.6e} | energy ~ {rep.energy:.6e} | max |grad w| in D ~ "

@@ -35,6 +35,8 @@ class EllipseProblem:
     tol: float = 1e-6
     max_iter: int = -1
     norm: str = "weighted"  # "weighted" (stage1..4) or "unweighted" (stage0)
+    # constant shift σ ≥ 0 of the operator: (A + σI) w = B, i.e. −Δu + σu = f (0.0: −Δu = f, today's code bit for bit)
+    shift: float = 0.0
 
     # ---- derived quantities (same formulas as csrc/include/pe/problem.hpp)
     @property
@@ -72,7 +74,16 @@ class EllipseProblem:
     def with_grid(self, M: int, N: int) -> "EllipseProblem":
         return dataclasses.replace(self, M=M, N=N)
 
+    def check_shift(self) -> float:
+        """The shift as a float — or ValueError: not finite, or negative (an indefinite system)."""
+        s = float(self.shift)
+        if not math.isfinite(s) or s < 0.0:
+            raise ValueError(f"shift must be finite and >= 0 (got {self.shift}): a negative shift makes the system "
+                             "indefinite")
+        return s
+
     def to_native(self):
+        shift = self.check_shift()  # (before any work, on every backend)
         nat = native()
         p = nat.Problem()
         p.M, p.N = int(self.M), int(self.N)
@@ -83,6 +94,7 @@ class EllipseProblem:
         p.tol = self.tol
         p.max_iter = int(self.max_iter)
         p.norm = nat.Norm.Unweighted if self.norm == "unweighted" else nat.Norm.Weighted
+        p.shift = shift
         return p
 
 

@@ -109,28 +109,33 @@ def assemble(prob: EllipseProblem, device="cpu", *, rhs=None):
     return t(a), t(b), t(B)
 
 
-def apply_A(p, a, b, h1, h2):
-    """(A p) on interior nodes; boundary rows/cols of the result are 0."""
+def apply_A(p, a, b, h1, h2, shift: float = 0.0):
+    """(A p) on interior nodes; boundary rows/cols of the result are 0.
+    shift σ ≠ 0 (EllipseProblem.shift): A_σ p = (Ax + Ay) + σ·p, the tree of
+    csrc/include/pe/fields.hpp (one multiply, one add; 0 keeps Ax + Ay)."""
     out = torch.zeros_like(p)
     pc = p[1:-1, 1:-1]
     Ax = (-1.0 / h1) * (_div(a[2:, 1:-1] * (p[2:, 1:-1] - pc), h1) - _div(a[1:-1, 1:-1] * (pc - p[:-2, 1:-1]), h1))
     Ay = (-1.0 / h2) * (_div(b[1:-1, 2:] * (p[1:-1, 2:] - pc), h2) - _div(b[1:-1, 1:-1] * (pc - p[1:-1, :-2]), h2))
-    out[1:-1, 1:-1] = Ax + Ay
+    out[1:-1, 1:-1] = (Ax + Ay) + shift * pc if shift != 0.0 else Ax + Ay
     return out
 
 
 def residual(prob: EllipseProblem, W, rhs=None, device="cpu"):
     """B − A W as an (M+1, N+1) tensor (0 on the box boundary): W an interior
     (M-1, N-1) array or a full tensor, B = rhs (None: F) inside the ellipse
-    and 0 outside — the torch form of native.residual_field."""
+    and 0 outside — the torch form of native.residual_field (A + σI with
+    prob.shift = σ)."""
     a, b, B = assemble(prob, device, rhs=rhs)
-    return B - apply_A(embed(prob, W, device), a, b, prob.h1, prob.h2)
+    return B - apply_A(embed(prob, W, device), a, b, prob.h1, prob.h2, prob.check_shift())
 
 
-def diag(a, b, h1, h2):
-    """Jacobi diagonal D on interior nodes (0 elsewhere)."""
+def diag(a, b, h1, h2, shift: float = 0.0):
+    """Jacobi diagonal D on interior nodes (0 elsewhere); shift σ ≠ 0: D_σ = D + σ."""
     D = torch.zeros_like(a)
     D[1:-1, 1:-1] = _div(a[2:, 1:-1] + a[1:-1, 1:-1], h1 * h1) + _div(b[1:-1, 2:] + b[1:-1, 1:-1], h2 * h2)
+    if shift != 0.0:
+        D[1:-1, 1:-1] = D[1:-1, 1:-1] + shift
     return D
 
 
@@ -168,13 +173,15 @@ def pcg(prob: EllipseProblem, device="cpu", w0=None, max_iter: Optional[int] = N
         keep_history: bool = False, *, rhs=None, exact=None) -> TorchPCGResult:
     """Reference-algorithm Jacobi PCG (stage2 solve_mpi order of operations).
     l2_err / max_err: against the user's `exact` when given, else against the
-    analytic solution; with a user rhs and no `exact` there is nothing to
+    analytic solution; with a user rhs, or a shifted operator (prob.shift ≠ 0:
+    (A + σI) w = B, preconditioner D + σ), and no `exact` there is nothing to
     compare with: -1."""
     a, b, B = assemble(prob, device, rhs=rhs)
     h1, h2 = prob.h1, prob.h2
-    D = diag(a, b, h1, h2)
+    sigma = prob.check_shift()
+    D = diag(a, b, h1, h2, sigma)
     w = torch.zeros_like(B) if w0 is None else embed(prob, w0, device)
-    r = B - apply_A(w, a, b, h1, h2)
+    r = B - apply_A(w, a, b, h1, h2, sigma)
     r[0, :] = r[-1, :] = 0
     r[:, 0] = r[:, -1] = 0
     z = apply_Dinv(r, D)
@@ -185,7 +192,7 @@ def pcg(prob: EllipseProblem, device="cpu", w0=None, max_iter: Optional[int] = N
     converged = False
     k = 0
     for k in range(1, cap + 1):
-        Ap = apply_A(p, a, b, h1, h2)
+        Ap = apply_A(p, a, b, h1, h2, sigma)
         den = dot(Ap, p, h1, h2)
         if abs(den) < 1e-15:
             break
@@ -208,7 +215,7 @@ def pcg(prob: EllipseProblem, device="cpu", w0=None, max_iter: Optional[int] = N
     if exact is not None:
         l2, mx = error_vs_analytic(prob, w, embed(prob, exact, device))
     else:
-        l2, mx = error_vs_analytic(prob, w) if rhs is None else (-1.0, -1.0)
+        l2, mx = error_vs_analytic(prob, w) if rhs is None and sigma == 0.0 else (-1.0, -1.0)
     return TorchPCGResult(k, converged, w, l2, mx, hist)
 
 

@@ -91,6 +91,8 @@ class SolveReport:
     integral: float = -1.0
     energy: float = -1.0
     grad_max: float = -1.0
+    # the problem's shift σ of (A + σI) w = B (to_dict() / --json carry it only when it is non-zero)
+    shift: float = 0.0
 
     @property
     def iters_per_s(self) -> float:
@@ -103,6 +105,8 @@ class SolveReport:
         d.pop("w", None)
         d.pop("grad", None)
         d["iters_per_s"] = self.iters_per_s
+        if not d.get("shift"):
+            d.pop("shift", None)
         return d
 
 
@@ -231,7 +235,8 @@ def _report(backend, prob, res, ranks, threads, init, w=None, rank=0) -> SolveRe
         resident_fallback=bool(getattr(res, "resident_fallback", False)),
         res_true=float(getattr(res, "res_true", -1.0)), res_rec=float(getattr(res, "res_rec", -1.0)),
         res_gap=float(getattr(res, "res_gap", -1.0)),
-        b_norm=float(getattr(res, "b_norm", -1.0)), restarts=int(getattr(res, "restarts", 0)))
+        b_norm=float(getattr(res, "b_norm", -1.0)), restarts=int(getattr(res, "restarts", 0)),
+        shift=float(prob.shift))
 
 
 def _grad_mode(return_grad, on_device: bool, backend: str = "hip"):
@@ -273,6 +278,16 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
     resumed solve (``resume=``) needs the same ``rhs`` (and ``exact``) again
     and ignores ``w0``.  None keeps the built-in constant F / ``init`` path bit
     for bit.
+
+    ``prob.shift`` = σ > 0 (every backend) solves (A + σI) w = B, the discrete
+    −Δu + σu = f, at every interior node of the box, with the preconditioner
+    D + σ; the stop rule, norms and statuses are unchanged.  The analytic
+    solution does not apply: ``l2_err`` / ``max_err`` are −1 unless ``exact``
+    is given.  The device backends run the classic two-kernel path (``algo``
+    "auto" or "classic"; the single-sweep kernels refuse a shift with
+    ValueError).  A resumed solve needs the same shift again: checkpoints do
+    not hold it.  σ must be finite and ≥ 0 (ValueError); 0 is today's solve
+    bit for bit.
 
     ``exact`` (every backend, same form): the solution to report the error
     against — a manufactured solution u with ``rhs`` = −Δu, say.  Then
@@ -354,7 +369,7 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
         rep = SolveReport("torch", prob.M, prob.N, 1, 1, 1, 1, r.iters, r.converged, False,
                           r.history[-1] if r.history else 0.0, timers, r.l2_err, r.max_err, -1.0,
                           "zero" if w0 is None else "field",
-                          r.w[1:-1, 1:-1].cpu().numpy() if return_w else None)
+                          r.w[1:-1, 1:-1].cpu().numpy() if return_w else None, shift=float(prob.shift))
         if grad:
             g, *stats = torch_ref.gradient(prob, r.w)
             _set_grad(rep, stats, g.cpu().numpy() if grad is True else None)
@@ -459,7 +474,7 @@ def _operator(prob, v, rhs, residual_, backend, ranks, threads, decomp, out, dev
             s = float((f * f).sum())
         else:
             a, b, _ = torch_ref.assemble(prob, device)
-            f = torch_ref.apply_A(V, a, b, prob.h1, prob.h2)[1:-1, 1:-1]
+            f = torch_ref.apply_A(V, a, b, prob.h1, prob.h2, prob.shift)[1:-1, 1:-1]
             s = float((V[1:-1, 1:-1] * f).sum())
         return FieldResult(f.cpu().numpy() if want else None, prob.h1 * prob.h2 * s)
     if backend == "hip-group":
