@@ -89,7 +89,7 @@ def fp64_norms(prob, w, f):
     """‖B − A w‖_E and ‖B‖_E with the user B (f masked by the ellipse) and
     max |w| outside D, in fp64 on the CPU, of the interior array w."""
     M, N = prob.M, prob.N
-    a, b, _ = norm_checks.assembled(M, N)
+    a, b, _ = norm_checks.assembled(prob)
     B = torch_ref.assemble(prob, rhs=f)[2]
     W = torch.zeros(M + 1, N + 1, dtype=torch.float64)
     W[1:M, 1:N] = torch.from_numpy(np.ascontiguousarray(w))

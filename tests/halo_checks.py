@@ -71,10 +71,16 @@ SINGLE_2D = [_case(23, 23, 4, "2x2", "auto", 9, "exchange", o, SINGLE) for o in 
 VIRTUAL = [(25, 25, 4, "2x2", 9, THREE), (26, 99, 4, "2x2", 12, THREE), (26, 99, 4, "2x2", 13, THREE),
            (27, 148, 6, "2x3", 12, THREE), (23, 23, 4, "2x2", 9, SINGLE)]
 
+# Virtual ranks on family members (test_sweep_family.py): block seams and the one-column last strip in front of an
+# UP neighbour, through nodes with interior coefficients at the box edge
+FAMILY_VIRTUAL = [v + (m,) for m in sweep_checks.SHORT_MEMBERS for v in (VIRTUAL[0], VIRTUAL[1], VIRTUAL[4])]
+
 CASES = TWO_SLABS + THREE_SLABS + THREE_2D + SINGLE_2D
 
 # every (kind, M, N, K) whose reference a case above is compared with
 REFERENCE_CASES = sorted({(KIND[c[7]], c[0], c[1], c[5]) for c in CASES} | {(KIND[v[5]], v[0], v[1], v[4]) for v in VIRTUAL})
+
+FAMILY_REFERENCE_CASES = sorted({(KIND[v[5]], v[0], v[1], v[4], v[6]) for v in FAMILY_VIRTUAL})
 
 # (M, N, ranks, decomp) -> rows per block along x, columns per block along y: what each shape is there for
 BLOCKS = {
@@ -96,11 +102,12 @@ def case_id(c):
     return f"{M}x{N}-{nproc}-{decomp}-{algo}-K{K}-{env['PE_HALO']}-ov{env['PE_OVERLAP']}"
 
 
-def _w_deviation(tag, M, N, K, kind, w):
+def _w_deviation(tag, M, N, K, kind, w, member=None):
     """max |w − w_ref| against the bound f_tol · max |w_ref|; returns (relative
-    deviation, bound, reference)."""
+    deviation, bound, reference).  member: a sweep_checks.FAMILY name (None:
+    the reference problem)."""
     f_tol = sweep_checks.KINDS[kind][6]
-    ref = sweep_checks.reference("single", M, N, K)
+    ref = sweep_checks.reference("single", M, N, K, member)
     want = ref.w[1:M, 1:N].numpy()
     assert w.shape == want.shape, (tag, w.shape)
     return float(np.abs(w - want).max() / np.abs(want).max()), f_tol, ref
@@ -161,17 +168,17 @@ def check_case(case, tmp_path):
     return dev
 
 
-def check_virtual(M, N, ranks, decomp, K, expect):
+def check_virtual(M, N, ranks, decomp, K, expect, member=None):
     """K iterations on virtual ranks of one process (backend hip-group): w
     against the same reference and bound."""
     rows, cols = BLOCKS[(M, N, ranks, decomp)]
-    prob = EllipseProblem(M, N)
+    prob = sweep_checks.problem(M, N, member)
     prob.max_iter = K
     rep = solve(prob, backend="hip-group", ranks=ranks, decomp=decomp, check_tol=False, return_w=True)
     assert rep.Px == len(rows) and rep.Py == len(cols) and rep.algo == expect, (rep.Px, rep.Py, rep.algo)
     assert rep.iters == K and not rep.converged, (rep.iters, rep.converged)
-    tag = f"{M}x{N}-{ranks}-{decomp}-K{K}-virtual"
-    dev_w, f_tol, _ = _w_deviation(tag, M, N, K, KIND[expect], rep.w)
+    tag = f"{M}x{N}{'-' + member if member else ''}-{ranks}-{decomp}-K{K}-virtual"
+    dev_w, f_tol, _ = _w_deviation(tag, M, N, K, KIND[expect], rep.w, member)
     print(f"halo-dev {tag} algo={rep.algo} path='virtual ranks' w/bound={dev_w / f_tol:.2e} w_rel={dev_w:.2e}")
     assert dev_w <= f_tol, (tag, dev_w, f_tol)
     return dev_w / f_tol

@@ -16,15 +16,21 @@ from poisson_ellipse_openmp_mpi_cuda_amd.ops import torch_ref
 
 
 @functools.lru_cache(maxsize=None)
-def assembled(M, N):
-    return torch_ref.assemble(EllipseProblem(M, N))
+def _assembled(M, N, A1, B1, A2, B2, cx, cy, F):
+    return torch_ref.assemble(EllipseProblem(M, N, A1=A1, B1=B1, A2=A2, B2=B2, cx=cx, cy=cy, F=F))
+
+
+def assembled(prob):
+    """a, b, B of the problem's own box and ellipse; computed once per problem."""
+    assert prob.shift == 0.0  # (A + σI is shift_checks' subject)
+    return _assembled(prob.M, prob.N, prob.A1, prob.B1, prob.A2, prob.B2, prob.cx, prob.cy, prob.F)
 
 
 def fp64_norms(prob, w):
     """‖B − A w‖_E, ‖B‖_E, the L2 and max error in D and max |w| over the
     interior nodes outside D, in fp64 on the CPU, of the interior array w."""
     M, N = prob.M, prob.N
-    a, b, B = assembled(M, N)
+    a, b, B = assembled(prob)
     W = torch.zeros(M + 1, N + 1, dtype=torch.float64)
     W[1:M, 1:N] = torch.from_numpy(np.ascontiguousarray(w))
     hh = prob.h1 * prob.h2

@@ -17,6 +17,7 @@ import subprocess
 import pytest
 
 import layout_checks
+import sweep_checks
 
 from poisson_ellipse_openmp_mpi_cuda_amd import EllipseProblem
 from poisson_ellipse_openmp_mpi_cuda_amd.parallel import decomp as D
@@ -33,12 +34,12 @@ def _default_name(steps, nx, ny):
     return "lpt" if steps < 3 or npts >= 5e7 else "fill" if npts >= 2.5e7 else "equal"
 
 
-def _layout(nat, M, N, P=1, spec="device", rank=0, steps=3, ti=None, order=0, overlap=False, force="", **kw):
+def _layout(nat, M, N, P=1, spec="device", rank=0, steps=3, ti=None, order=0, overlap=False, force="", member=None, **kw):
     blk = nat.decompose(M, N, D.grid(P, M, N, spec), rank)
     if ti is None:  # the construction's untuned heights (three-step)
         npts = blk.nx * blk.ny
         ti = 448 if npts > 1 << 26 else 112 if npts >= 1 << 25 else 80 if npts >= 1 << 24 else 48
-    lay = nat.item_layout(EllipseProblem(M, N).to_native(), blk, steps, ti, order=order, overlap=overlap,
+    lay = nat.item_layout(sweep_checks.problem(M, N, member).to_native(), blk, steps, ti, order=order, overlap=overlap,
                           layout=_default_name(steps, blk.nx, blk.ny), force_layout=force, **kw)
     return blk, lay
 
@@ -105,6 +106,27 @@ def test_small_shapes(nat, M, N, P, spec, rank, steps, ti, order, ov, lay):
         assert (per - 1) * l["waves"] < len(ent) <= per * l["waves"]
         if (M, N) == (40, 40):
             layout_checks.equal_balance(l["entries"], l["load"], l["waves"])
+
+
+# the three-step cases of test_sweep_family.py whose item kinds sweep_checks.check_item_kinds pins: (member, M, N, ti, layout)
+FAMILY_KINDS = ([("cover", 66, 49, 48, "")] + [(m, 40, 200, 48, "") for m in sweep_checks.FAMILY]
+                + [(m,) + sweep_checks.SHORT_GRID + (48, "") for m in ("cover", "cut_y", "cut_xy", "offc")]
+                + [(m,) + sweep_checks.SHORT_GRID + (ti, lay) for m in sweep_checks.SHORT_MEMBERS
+                   for ti in sweep_checks.SHORT_THREE[1] for lay in sweep_checks.SHORT_THREE[2]])
+
+
+@pytest.mark.parametrize("member,M,N,ti,lay", FAMILY_KINDS)
+def test_family_cases_hold_their_item_kinds(nat, member, M, N, ti, lay):
+    """The family members' three-step cases are there for uniform items on
+    edge strips (the reference problem's lists at these shapes are band items
+    only): the covering ellipse is nothing else, the cut and off-centre ones
+    mix them with band items, 40×200 adds an inner strip.  Were the planner to
+    stop flagging them, the MI355X test would compare kernels it no longer
+    runs; it asserts the same from the live solver's list."""
+    blk, l = _layout(nat, M, N, ti=ti, force=lay, member=member)
+    _check(nat, blk, l, 3, False)
+    assert l["name"] == (lay or "equal")
+    sweep_checks.check_item_kinds(l["entries"], M, N, member)
 
 
 def _rebuild(nat, c):

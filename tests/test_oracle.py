@@ -20,7 +20,8 @@ VARIANTS = [
     (1000, 37, {}),
     (512, 512, dict(A2=-1.0, B2=1.0, cy=1.0)),                               # circle
     (300, 200, dict(A1=-2.0, B1=2.0, A2=-1.0, B2=1.0, cx=0.25, cy=1.0)),     # wide ellipse
-]
+    # members that cut or cover the box (sweep_checks.FAMILY): interior coefficients at the box edge
+] + [(M, N, kw) for kw in sweep_checks.FAMILY.values() for M, N in ((66, 49), (130, 97), (34, 250))]
 
 
 @pytest.mark.parametrize("M,N,kw", VARIANTS)
@@ -137,21 +138,32 @@ def test_three_step_stop_test_matches_reference_history():
     np.testing.assert_allclose(diffs, ref.history, rtol=1e-7)
 
 
-@pytest.mark.parametrize("kind,M,N,count", sweep_checks.REFERENCE_CASES)
-def test_edge_shape_references_agree(kind, M, N, count):
+def _with_members(cases, family_cases):
+    """The reference problem's cases under the ids they always had, then the family's (…-member)."""
+    return ([pytest.param(*c, None, id="-".join(str(v) for v in c)) for c in cases]
+            + [pytest.param(*c, id="-".join(str(v) for v in c)) for c in family_cases])
+
+
+@pytest.mark.parametrize("kind,M,N,count,member",
+                         _with_members(sweep_checks.REFERENCE_CASES, sweep_checks.FAMILY_REFERENCE_CASES))
+def test_edge_shape_references_agree(kind, M, N, count, member):
     """The references the MI355X sweep tests compare the kernels with
     (sweep_checks: edge shapes, short-item grid), at their counts: the
     multi-step recurrences equal the single-sweep one to 1e-11 of the plane
     maximum on w, r and p, and the single sweep equals the reference PCG loop
     to 1e-13 on w — ten times inside the kernels' tolerances, so no shape
     brings a reference that fails on its own (an iterate near convergence,
-    where the moment forms' rounding takes over)."""
+    where the moment forms' rounding takes over).  The same gate for the
+    family members of test_sweep_family.py (sweep_checks.FAMILY): a (member,
+    shape, count) that does not pass here is not compared on the device.  All
+    pass at the reference problem's counts but tiny on the short-item grid,
+    which converges in 19 iterations and is left out of that grid."""
     steps = sweep_checks.KINDS[kind][1]
     K = steps * count
-    prob = EllipseProblem(M, N)
-    one = sweep_checks.reference("single", M, N, K)
+    prob = sweep_checks.problem(M, N, member)
+    one = sweep_checks.reference("single", M, N, K, member)
     if steps > 1:
-        multi = sweep_checks.reference(kind, M, N, count)
+        multi = sweep_checks.reference(kind, M, N, count, member)
         for name in ("w", "r", "p"):
             a, b = getattr(multi, name), getattr(one, name)
             assert float((a - b).abs().max()) <= 1e-11 * float(b.abs().max()), name
@@ -160,8 +172,9 @@ def test_edge_shape_references_agree(kind, M, N, count):
     assert float((one.w - ref.w).abs().max()) <= 1e-13 * float(ref.w.abs().max())
 
 
-@pytest.mark.parametrize("kind,M,N,K", halo_checks.REFERENCE_CASES)
-def test_halo_case_references_agree(kind, M, N, K):
+@pytest.mark.parametrize("kind,M,N,K,member",
+                         _with_members(halo_checks.REFERENCE_CASES, halo_checks.FAMILY_REFERENCE_CASES))
+def test_halo_case_references_agree(kind, M, N, K, member):
     """The references of the multi-rank cases (halo_checks), at their iteration
     counts: the reference PCG loop capped at K ends there unconverged, the
     single sweep — what the cases are compared with — equals it to 1e-13 of
@@ -171,13 +184,13 @@ def test_halo_case_references_agree(kind, M, N, K):
     multi-step vs single sweep at most 3.3e-13: each at least 30 times inside
     the kernels' bounds.)"""
     steps = sweep_checks.KINDS[kind][1]
-    prob = EllipseProblem(M, N)
-    one = sweep_checks.reference("single", M, N, K)
+    prob = sweep_checks.problem(M, N, member)
+    one = sweep_checks.reference("single", M, N, K, member)
     ref = torch_ref.pcg(prob, max_iter=K)
     assert ref.iters == K and not ref.converged
     assert float((one.w - ref.w).abs().max()) <= 1e-13 * float(ref.w.abs().max())
     if steps > 1 and K % steps == 0:
-        multi = sweep_checks.reference(kind, M, N, K // steps)
+        multi = sweep_checks.reference(kind, M, N, K // steps, member)
         for name in ("w", "r", "p"):
             a, b = getattr(multi, name), getattr(one, name)
             assert float((a - b).abs().max()) <= 1e-11 * float(b.abs().max()), name
