@@ -10,7 +10,7 @@ Arrays use the reference's global indexing: shape (M+1, N+1), index [i, j]
 for node (x_i, y_j); interior unknowns are [1:M, 1:N]; the box boundary is
 held at 0 (Dirichlet).
 
-User fields (keyword-only ``rhs``, ``w0`` of assemble / pcg / single_sweep /
+User fields (keyword-only ``rhs``, ``w0`` of assemble / pcg / classic / single_sweep /
 two_step / three_step) are INTERIOR arrays of shape (M-1, N-1), numpy or
 torch, entry [i-1, j-1] at node (x_i, y_j) — the shape every backend takes
 and ``return_w`` / ``--dump`` produce.  ``rhs`` is masked by the ellipse
@@ -217,6 +217,55 @@ def pcg(prob: EllipseProblem, device="cpu", w0=None, max_iter: Optional[int] = N
     else:
         l2, mx = error_vs_analytic(prob, w) if rhs is None and sigma == 0.0 else (-1.0, -1.0)
     return TorchPCGResult(k, converged, w, l2, mx, hist)
+
+
+@dataclass
+class ClassicState:
+    iters: int
+    sums: list    # per iteration k = 1 .. K: the unweighted (Σ Ap_k·p_k, Σ p_k·p_k, Σ z_k·r_k)
+    alpha: list   # α_k, β_k for k = 1 .. K (β_1 = 0: p_1 = z_0)
+    beta: list
+    r: torch.Tensor
+    p: torch.Tensor   # p_K, the direction iteration K used
+    w: torch.Tensor
+
+
+def classic(prob: EllipseProblem, iters: int, device="cpu", *, rhs=None, w0=None) -> ClassicState:
+    """The reference loop (pcg) without its stop test, for exactly `iters`
+    iterations, with prob.shift: the state the classic two-kernel device path
+    (csrc/hip/kernels.hip kF + kG) holds then.  Iteration k: p_k = z_{k-1} +
+    β_k p_{k-1}, the sums Σ Ap_k·p_k and Σ p_k·p_k (DevState::red_F), α_k,
+    w_k = w_{k-1} + α_k p_k, r_k = r_{k-1} − α_k A p_k, Σ z_k·r_k
+    (DevState::red_G).  p is p_K — what kF stored last — not the p_{K+1} pcg
+    forms at the end of its loop; the sums are unweighted (no h1 h2)."""
+    a, b, B = assemble(prob, device, rhs=rhs)
+    h1, h2 = prob.h1, prob.h2
+    sigma = prob.check_shift()
+    D = diag(a, b, h1, h2, sigma)
+    inner = lambda u, v: float((u[1:-1, 1:-1] * v[1:-1, 1:-1]).sum())  # noqa: E731  (unweighted)
+    w = torch.zeros_like(B) if w0 is None else embed(prob, w0, device)
+    r = B - apply_A(w, a, b, h1, h2, sigma)
+    r[0, :] = r[-1, :] = 0
+    r[:, 0] = r[:, -1] = 0
+    z = apply_Dinv(r, D)
+    p = torch.zeros_like(B)
+    zr = inner(z, r)
+    zr_old = 0.0
+    sums, alphas, betas = [], [], []
+    for k in range(1, iters + 1):
+        beta = 0.0 if k == 1 else (zr * h1 * h2) / (zr_old * h1 * h2)
+        p = z + beta * p
+        Ap = apply_A(p, a, b, h1, h2, sigma)
+        s_den, s_pp = inner(Ap, p), inner(p, p)
+        alpha = (zr * h1 * h2) / (s_den * h1 * h2)
+        w = w + alpha * p
+        r = r - alpha * Ap
+        z = apply_Dinv(r, D)
+        zr_old, zr = zr, inner(z, r)
+        sums.append((s_den, s_pp, zr))
+        alphas.append(alpha)
+        betas.append(beta)
+    return ClassicState(iters, sums, alphas, betas, r, p, w)
 
 
 @dataclass

@@ -120,14 +120,15 @@ def check_norms(tag, prob, rep, f, three):
     return dev
 
 
-def solver(nat, M, N, algo, variant=0, fields=True):
-    """A single-rank solver (convergence test off) with both fields set."""
+def solver(nat, M, N, algo, variant=0, fields=True, prob=None):
+    """A single-rank solver (convergence test off) with both fields set; prob:
+    another M×N problem than the reference one (a shift, a family member)."""
     opt = nat.SolveOptions()
     opt.algo = algo
     opt.variant = variant
     opt.check_tol = False
     blk = D.block(M, N, 1, 0)
-    s = nat.DeviceSolver(EllipseProblem(M, N).to_native(), blk, None, opt)
+    s = nat.DeviceSolver((prob or EllipseProblem(M, N)).to_native(), blk, None, opt)
     if fields:
         set_fields(nat, s, M, N, rhs(M, N), w0(M, N))
     return s

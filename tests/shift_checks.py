@@ -34,7 +34,8 @@ from poisson_ellipse_openmp_mpi_cuda_amd import EllipseProblem, native, solve
 SIGMAS = (0.75, 40.0)
 STRETCHED_KW = oc.STRETCHED[1][2]  # cx = 0.25 in the box [-2, 2] × [-1, 1], here at 96 × 64
 # (40, 40); ny = 129: a last strip of one column and an odd tail lane; ny = 128: exactly one full strip, nx = 69
-# crosses a segment; (65, 258); one stretched problem
+# is nine items (at 8 rows per item no item reaches a second segment: test_classic_gpu.py forces the height for
+# that); (65, 258); one stretched problem
 SHAPES = [(40, 40, None), (9, 130, None), (70, 129, None), (65, 258, None), (96, 64, STRETCHED_KW)]
 IDS = [f"{M}x{N}{'s' if kw else ''}" for M, N, kw in SHAPES]
 
