@@ -487,6 +487,19 @@ PYBIND11_MODULE(_native, m) {
       py::arg("ov_debug") = 0, py::arg("force_layout") = "",
       "the item list a solver of this block would walk (the defaults: two 4-wave workgroups on each of 256 CUs)");
 
+  m.def(
+      "planner_row_classes",
+      [](const Problem& P, const Block& blk, int steps) {
+        const LayoutPlanner pl = block_planner(P, blk, steps);
+        const std::vector<int>& rc = pl.row_classes();
+        const int64_t R = int64_t(rc.size() / 4);
+        py::array_t<int> a({R, int64_t(4)});
+        std::copy(rc.begin(), rc.begin() + R * 4, a.mutable_data());
+        return py::make_tuple(a, pl.tab_lo());
+      },
+      py::arg("prob"), py::arg("block"), py::arg("steps"),
+      "the row classes item_layout plans from: ({in_lo, in_hi, out_lo, out_hi} per local row, first local row)");
+
   // ---- device (HIP / RCCL) ----------------------------------------------
   m.def("device_count", &device_count);
   m.def("set_device", &set_device);

@@ -204,7 +204,13 @@ struct LayoutPlanner::Ctx {
     if (lo > hi) return false;                 // no interior column
     return !(r[0] <= J && r[1] >= J + Wc - 1);  // some interior, some not
   }
-  // Per strip, prefix counts of the band / mixed rows q = 1-H .. nx+H (the
+  // (a row wholly interior in the strip's columns: the class of a uniform row)
+  bool row_inner_x(int64_t q, int s) const {
+    const int64_t J = -(HL - 1) + int64_t(s) * g.fsw;
+    const int* r = row_class(q);
+    return r && r[0] <= J && r[1] >= J + Wc - 1;
+  }
+  // Per strip, prefix counts of the band / mixed / wholly interior rows q = 1-H .. nx+H (the
   // windows of every item; built once per planner: the rows-per-item tuning
   // re-lays out up to 11 times, and evaluating the rows one by one per item
   // took 4.5-5.7 ms per layout at 4096², inside T_solver).
@@ -212,12 +218,15 @@ struct LayoutPlanner::Ctx {
     if (!P.pgen_.empty()) return;
     P.pgen_.assign(size_t(ns) * size_t(R + 1), 0);
     P.pmix_.assign(size_t(ns) * size_t(R + 1), 0);
+    P.pinn_.assign(size_t(ns) * size_t(R + 1), 0);
     for (int s = 0; s < ns; ++s) {
       int* gp = &P.pgen_[size_t(s) * size_t(R + 1)];
       int* m = &P.pmix_[size_t(s) * size_t(R + 1)];
+      int* in = &P.pinn_[size_t(s) * size_t(R + 1)];
       for (int64_t i = 0; i < R; ++i) {
         gp[i + 1] = gp[i] + (row_gen_x(q0 + i, s) ? 1 : 0);
         m[i + 1] = m[i] + (row_mixed_x(q0 + i, s) ? 1 : 0);
+        in[i + 1] = in[i] + (row_inner_x(q0 + i, s) ? 1 : 0);
       }
     }
   }
@@ -228,14 +237,21 @@ struct LayoutPlanner::Ctx {
   }
   int ngen(int64_t a, int64_t b, int s) const { return among(P.pgen_, a, b, s); }
   int nmix(int64_t a, int64_t b, int s) const { return among(P.pmix_, a, b, s); }
+  int ninn(int64_t a, int64_t b, int s) const { return among(P.pinn_, a, b, s); }
   // per-item cost: rows ib-H .. ie+H, band rows weighted
   double rows_cost(int64_t ib, int64_t ie, int s) const {
     const int64_t n = ie - ib + 1 + 2 * H, ng = ngen(ib - H, ie + H, s);
     return double(n - ng) + double(ng) * gen_cost;
   }
   bool rows_band(int64_t ib, int64_t ie, int s) const { return ngen(ib - H, ie + H, s) > 0; }
+  // ... and all of one class: the uniform march takes its coefficients once
+  // per item, from the window's first row.  (No window of rows that are
+  // uniform in a strip holds both classes — vertical neighbours share a face,
+  // so a band row lies between — and the test turns that into a guarantee.)
   bool rows_uniform(int64_t ib, int64_t ie, int s) const {
-    return ngen(ib - H, ie + H, s) == 0 && nmix(ib - H, ie + H, s) == 0;
+    const int64_t a = ib - H, b = ie + H;
+    const int in = ninn(a, b, s);
+    return ngen(a, b, s) == 0 && nmix(a, b, s) == 0 && (in == 0 || in == int(b - a + 1));
   }
   double item_cost(int ch, int s) const {
     const int64_t ib = 1 + int64_t(ch) * ti, ie = std::min<int64_t>(ib + ti - 1, nx);

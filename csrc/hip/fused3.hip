@@ -385,8 +385,8 @@ __device__ __forceinline__ void sweep3_finalize(const KParams& k, DevState* st, 
 
 // Item kinds (list entry flags): band items (a boundary-band row in the
 // window: coefficients from the chord tables, LDS face ring), uniform items
-// (kUniBit: every row of the window lies wholly inside or wholly outside the
-// interior in this strip — the row's coefficients are three scalars) and
+// (kUniBit: the rows of the window lie all wholly inside or all wholly outside
+// the interior in this strip — the item's coefficients are three scalars) and
 // mixed plain items (per-lane interior tests).
 enum { kMixed = 0, kBand = 1, kUniform = 2 };
 
@@ -402,9 +402,10 @@ struct M3Ctx {
   bool lv0, o0, fix;
   bool scol;          // the lane's column is not past ny (2-D blocks: past ny are the UP neighbour's)
   double lf0;         // lv0 as 1.0 / 0.0 (uniform items of the edge strips)
-  double oih1, oih2;  // inv_eps / h1², inv_eps / h2² (uniform exterior rows)
-  double ih1, ih2, din, dout;  // 1/h1², 1/h2², 1/D interior / exterior (copies: a select between
-                               // kernel-argument fields compiles to a scalar load per use)
+  double ih1, ih2, dcl;  // uniform items: the face coefficient of the item's class over h1², over h2², and its
+                         // 1/D.  One class per item: a window that is uniform in its strip never holds both
+                         // (vertical neighbours share a face, and a face is 1 or 1/ε exactly only away from
+                         // the band), and the planner's rows_uniform requires it.
   int rlo, rhi;       // local rows of the global interior: rlo ≤ q ≤ rhi
   double zc1, zc2, zc3, a1, a2, a3, b1, b2, b3, w1, w2, w3;
 };
@@ -450,13 +451,8 @@ struct Pre3 {
 };
 
 template <bool STEADY>
-__device__ __forceinline__ URow urow(const M3Ctx& c, const RowCtx& rx, int q) {
-  const int l = (q - rx.segbase) & 63;
-  const bool in = (rx.allin >> l) & 1ull;
-  URow r;
-  r.ih1 = in ? c.ih1 : c.oih1;
-  r.ih2 = in ? c.ih2 : c.oih2;
-  r.d = in ? c.din : c.dout;
+__device__ __forceinline__ URow urow(const M3Ctx& c, int q) {
+  URow r{c.ih1, c.ih2, c.dcl};
   if constexpr (!STEADY) {
     if (!(q >= c.rlo && q <= c.rhi)) r.d = 0.0;
   }
@@ -564,13 +560,25 @@ __device__ __forceinline__ void step3(const KParams& k, const M3Ctx& c, M3Rings&
   // the operator at row q (band ring slots sl, sln) and 1/D of the node
   auto op = [&](int q, int sl, int sln, double um, double u0, double un, double& d) {
     if constexpr (UNI) {
-      const URow r = urow<STEADY>(c, rx, q);
+      const URow r = urow<STEADY>(c, q);
       d = r.d;
       return lapu(r, um, u0, un);
     } else {
       return apply_row1<BAND>(k, rx, tvw, q, c0, sl, sln, um, u0, un, d);
     }
   };
+  // p_i = zc·z + β·p_{i-1}.  Under fast contraction either product may become
+  // the fma's addend, and the compiler's choice moved from copy to copy of
+  // this code whenever the march around it changed.  The uniform kind's is
+  // fixed as it stood when its outputs were pinned bit for bit
+  // (tests/test_sweep_pins.py): zc·z rounded, then β·p added fused — except in
+  // stage A of the steady groups' last steps (from JJ = 4 on interior strips,
+  // JJ = 3 in the push variant on every strip), where β·p is the rounded one.
+  auto pnext = [&](double zc, double z, double b, double p, bool zfused) -> double {
+    if constexpr (UNI) return zfused ? __builtin_fma(zc, z, b * p) : __builtin_fma(b, p, zc * z);
+    else return zc * z + b * p;
+  };
+  constexpr bool kAzf = STEADY && (PUSH ? JJ >= 3 : (!EDGE && JJ >= 4));
   // ---- A: row t ----
   const double rin = x.RQ[xs], pin = x.PQ[xs], wrow = x.WQ[ws];
   if constexpr (STEADY) {  // running row pointers (M3Ptr); PUSH: the halo rows keep their own formula
@@ -594,10 +602,10 @@ __device__ __forceinline__ void step3(const KParams& k, const M3Ctx& c, M3Rings&
   }
   {
     double d;
-    if constexpr (UNI) d = urow<STEADY>(c, rx, t).d;
+    if constexpr (UNI) d = urow<STEADY>(c, t).d;
     else d = BAND ? enter_band1(k, rx, tvw, t, c0, bsl[0]) : dinv_plain1(k, rx, t, c0);
     const double z = zmask(t, rin, d);
-    x.P1[m0] = zc1 * z + c.b1 * pin;
+    x.P1[m0] = pnext(zc1, z, c.b1, pin, kAzf);
     x.RI[e0] = rin;
   }
   if (STEADY) __builtin_amdgcn_sched_barrier(0);  // (stage by stage, as the row tests of the generic steps)
@@ -610,7 +618,7 @@ __device__ __forceinline__ void step3(const KParams& k, const M3Ctx& c, M3Rings&
     const double z = zmask(q, r1, d);
     const double p1 = x.P1[m1];
     x.R1[e1] = r1;
-    x.P2[m1] = zc2 * z + c.b2 * p1;
+    x.P2[m1] = pnext(zc2, z, c.b2, p1, false);
     if (inr(q)) put(16, p1 * p1);
   }
   if (STEADY) __builtin_amdgcn_sched_barrier(0);
@@ -623,7 +631,7 @@ __device__ __forceinline__ void step3(const KParams& k, const M3Ctx& c, M3Rings&
     const double z = zmask(q, r2, d);
     const double p2 = x.P2[m2];
     x.R2[e0] = r2;
-    const double p3 = zc3 * z + c.b3 * p2;
+    const double p3 = pnext(zc3, z, c.b3, p2, false);
     x.P3[m2] = p3;
     if (own(q) && c.o0) {
       const double wn = wrow + w1 * x.P1[m2] + w2 * p2 + w3 * p3;
@@ -811,12 +819,6 @@ __device__ __forceinline__ void march3(const KParams& k, const Coef3& cf, bool f
   c.nx = int(k.nx);
   c.par = par;
   c.hrd = PUSH ? k.hrecv + int64_t(par ^ 1) * 2 * H3 * k.pitch : nullptr;
-  c.oih1 = uni(k.inv_eps * k.ih1sq);
-  c.oih2 = uni(k.inv_eps * k.ih2sq);
-  c.ih1 = k.ih1sq;
-  c.ih2 = k.ih2sq;
-  c.din = k.dinv_in;
-  c.dout = k.dinv_out;
   c.rlo = int(max<int64_t>(1 - k.gi0, -(1 << 30)));
   c.rhi = int(min<int64_t>(k.M - 1 - k.gi0, 1 << 30));
   c.zc1 = cf.zc[0];
@@ -844,6 +846,14 @@ __device__ __forceinline__ void march3(const KParams& k, const Coef3& cf, bool f
   if (KIND == kBand) load_strip_tables1(k, tvw, c.c0);
   if (use_pre) load_rows<KIND == kBand, WaveTV3, 64>(k, rx, tvw, c.t0, ie + H3 + 1, c.J, &pre.rc4);
   else load_seg(c.t0);
+  if constexpr (KIND == kUniform) {  // the item's class: its first window row's
+    const bool in = rx.allin & 1ull;
+    c.ih1 = in ? k.ih1sq : uni(k.inv_eps * k.ih1sq);
+    c.ih2 = in ? k.ih2sq : uni(k.inv_eps * k.ih2sq);
+    c.dcl = in ? k.dinv_in : k.dinv_out;
+  } else {
+    c.ih1 = c.ih2 = c.dcl = 0.0;  // (not read)
+  }
 
   M3Rings x;
   x.pushed = false;
@@ -894,8 +904,8 @@ __device__ __forceinline__ void march3(const KParams& k, const Coef3& cf, bool f
   // rows inside the item for all six steps (n ≥ 12, n ≤ rows + 4); the fill
   // and drain groups around them test rows.  Three loops, not one with a
   // branch: the merged ring state would cost a copy of every ring.
-  auto reload = [&](int n0) {
-    if (c.t0 + n0 + 6 - rx.segbase > 63) load_seg(c.t0 + n0 - H3);  // tall items: next row window
+  auto reload = [&](int n0) {  // tall items: next row window (uniform items read none after the first row's class)
+    if (KIND != kUniform && c.t0 + n0 + 6 - rx.segbase > 63) load_seg(c.t0 + n0 - H3);
   };
   M3Ptr rp;
   rp.pb = unsigned(c.pitch) * 8u;

@@ -133,7 +133,11 @@ bool DeviceSolver::placement_search(bool retry) {
   // profiles/r4_bench112.txt; 4.2 stopped at 0.743 ms candidates) — 4.45 TB/s
   // (≤ 0.724 ms) since round 6: 4.4 accepted a 0.7295 ms candidate and the
   // bench ran 3876 it/s against 4011-4136 with 0.701-0.722 ms picks
-  // (profiles/r6_placement.txt)
+  // (profiles/r6_placement.txt); 4.6 TB/s (≤ 0.700 ms) since round 9: the
+  // uniform march's shorter row step moved the classes to 0.668-0.684 and
+  // 0.710-0.713 ms, so 4.45 accepted the second class in half of the fresh
+  // processes, which then ran 3932-3946 it/s against 4232 with a first-class
+  // pick — below the code before it (profiles/r9_uniform_ab.txt)
   // Blocks of 24-50 M nodes (the 2-rank split of 8192²) stream slower per
   // byte: their best candidates are 0.396-0.400 ms per sweep at 33.5 M nodes =
   // 4.03-4.06 TB/s, so the three-step rate there is 4.0 TB/s — at 4.45 no
@@ -141,7 +145,7 @@ bool DeviceSolver::placement_search(bool retry) {
   // spacer past the first round's memory took 1-4 s of construction
   // (profiles/r6_placement.txt)
   const bool mid_large = pts < 50.0e6;
-  const double fast_tbs = steps_ >= 3 ? (mid_large ? 4.0 : 4.45) : sstep_ ? 4.7 : 4.9, max_s = 0.3;
+  const double fast_tbs = steps_ >= 3 ? (mid_large ? 4.0 : 4.6) : sstep_ ? 4.7 : 4.9, max_s = 0.3;
   if (tries <= 1) return true;
   // spacers are transient; never let the search take more than 40 % of the
   // free memory (several solvers may share the device)

@@ -301,10 +301,15 @@ struct URow {
   double ih1, ih2, d;
 };
 
-// The 5-point operator of a uniform row on the lane's column.
+// The 5-point operator of a uniform row on the lane's column.  A lane's
+// ur − u0 is its right neighbour's e = u0 − ul, operand for operand: taken
+// from that lane instead of shifting u0 both ways and subtracting twice.
+// Lane 63 gets 0 where it had 0 − u0; like the 0 it read for ur before, that
+// is wrong only in a halo lane, and moves one lane per nested operator
+// (six: lanes 58..63, inside the right halo).
 __device__ __forceinline__ double lapu(const URow& r, double um, double u0, double un) {
-  const double ul = dpp_shr1(u0), ur = dpp_shl1(u0);
-  return ((u0 - um) - (un - u0)) * r.ih1 + ((u0 - ul) - (ur - u0)) * r.ih2;
+  const double e = u0 - dpp_shr1(u0);
+  return ((u0 - um) - (un - u0)) * r.ih1 + (e - dpp_shl1(e)) * r.ih2;
 }
 
 __device__ __forceinline__ double dinv_plain1(const KParams& k, const RowCtx& rx, int q, int c0) {

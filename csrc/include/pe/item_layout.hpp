@@ -20,9 +20,9 @@ constexpr int kTImax = 62;       // max rows per work item (rows ib-1..ie+1 live
 // (general march); clear → the plain unrolled march.
 constexpr int kBandBit = 1 << 30;
 constexpr int kRowMask = kBandBit - 1;
-// Three-step sweep only: kUniBit set when every row ib-6 .. ie+6 of the item
-// lies wholly inside or wholly outside the interior in its strip's window
-// (the kernel's uniform-row march: three scalars per row, no lane tests).
+// Three-step sweep only: kUniBit set when the rows ib-6 .. ie+6 of the item
+// lie all wholly inside or all wholly outside the interior in its strip's
+// window (the kernel's uniform march: three scalars per item, no lane tests).
 constexpr int kUniBit = 1 << 29;
 constexpr int kRowMask3 = kUniBit - 1;
 constexpr int kFSW = 124;        // fused sweep: output columns per wave strip (128 loaded, 2-column halo per side)
@@ -97,6 +97,9 @@ class LayoutPlanner {
   // has: LEFT, RIGHT, DOWN, UP neighbours; rowcls: the block's row classes from local row g.tab_lo
   LayoutPlanner(const SweepGeometry& g, int64_t nx, int64_t ny, const bool has[4], std::vector<int> rowcls);
   ItemLayout build(const LayoutRequest& rq);
+  // the row classes the lists are planned from: {in_lo, in_hi, out_lo, out_hi} per local row, from row tab_lo()
+  const std::vector<int>& row_classes() const { return rowcls_; }
+  int64_t tab_lo() const { return g_.tab_lo; }
 
  private:
   struct Ctx;
@@ -104,7 +107,7 @@ class LayoutPlanner {
   int64_t nx_, ny_;
   bool has_[4];
   std::vector<int> rowcls_;
-  std::vector<int> pgen_, pmix_;  // per strip, prefix counts of the band / mixed rows (built at the first list)
+  std::vector<int> pgen_, pmix_, pinn_;  // per strip, prefix counts of the band / mixed / wholly interior rows (built at the first list)
   std::vector<std::array<int64_t, 4>> eq_runs_[2];  // equal-cost layout: runs {first row, rows, strip, kind} (no overlap / overlap)
 };
 
