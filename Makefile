@@ -25,8 +25,8 @@ HIPFLAGS  += $(COMMON) --offload-arch=$(ARCH) -ffp-contract=off -mcode-object-ve
              -fno-gpu-rdc -munsafe-fp-atomics
 LDLIBS    := -L$(ROCM)/lib -lamdhip64 -lrccl -lrocprofiler-sdk-roctx -lgomp -lpthread -Wl,-rpath,$(ROCM)/lib
 
-CORE_SRC  := csrc/core/decomp.cpp csrc/core/thread_comm.cpp csrc/core/report.cpp csrc/core/item_layout.cpp csrc/core/row_classes.cpp csrc/core/fields.cpp csrc/cpu/pcg_cpu.cpp
-HOST_SRC  := csrc/hip/device_solver.cpp csrc/hip/item_layout.cpp csrc/hip/placement.cpp csrc/hip/checkpoint.cpp csrc/hip/halo_path.cpp csrc/hip/rccl_comm.cpp csrc/hip/p2p_comm.cpp csrc/hip/runtime.cpp
+CORE_SRC  := csrc/core/decomp.cpp csrc/core/thread_comm.cpp csrc/core/report.cpp csrc/core/item_layout.cpp csrc/core/solver_plan.cpp csrc/core/row_classes.cpp csrc/core/fields.cpp csrc/cpu/pcg_cpu.cpp
+HOST_SRC  := csrc/hip/device_solver.cpp csrc/hip/env_knobs.cpp csrc/hip/item_layout.cpp csrc/hip/placement.cpp csrc/hip/checkpoint.cpp csrc/hip/halo_path.cpp csrc/hip/rccl_comm.cpp csrc/hip/p2p_comm.cpp csrc/hip/runtime.cpp
 HIP_SRC   := csrc/hip/kernels.hip csrc/hip/fused.hip csrc/hip/fused2.hip csrc/hip/fused3.hip csrc/hip/resident.hip csrc/hip/p2p.hip
 BIND_SRC  := csrc/bind/module.cpp
 
@@ -81,7 +81,13 @@ SAN_SRC   := $(CORE_SRC) csrc/apps/pe_cpu.cpp
 LAY_SRC   := csrc/core/item_layout.cpp csrc/core/row_classes.cpp csrc/core/decomp.cpp csrc/apps/pe_layout.cpp
 # (the field slicing helper: host index arithmetic; links no HIP)
 FLD_SRC   := csrc/core/fields.cpp csrc/core/decomp.cpp csrc/apps/pe_fields.cpp
-asan: $(BIN)/pe_cpu_asan $(BIN)/pe_layout_asan $(BIN)/pe_fields_asan
+# (the solver plan: host arithmetic over the block and the parsed knobs; links no HIP)
+PLAN_SRC  := csrc/core/solver_plan.cpp csrc/core/item_layout.cpp csrc/core/fields.cpp csrc/core/decomp.cpp csrc/apps/pe_plan.cpp
+asan: $(BIN)/pe_cpu_asan $(BIN)/pe_layout_asan $(BIN)/pe_fields_asan $(BIN)/pe_plan_asan
+$(BIN)/pe_plan_asan: $(PLAN_SRC) $(HEADERS)
+	@mkdir -p $(BIN)
+	$(CXX) -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -Icsrc/include -fno-omit-frame-pointer \
+	  -fsanitize=address,undefined -fno-sanitize-recover=undefined $(PLAN_SRC) -o $@
 $(BIN)/pe_fields_asan: $(FLD_SRC) $(HEADERS)
 	@mkdir -p $(BIN)
 	$(CXX) -O1 -g -std=c++17 -Wall -Wno-unknown-pragmas -Icsrc/include -fno-omit-frame-pointer \

@@ -500,6 +500,76 @@ PYBIND11_MODULE(_native, m) {
       py::arg("prob"), py::arg("block"), py::arg("steps"),
       "the row classes item_layout plans from: ({in_lo, in_hi, out_lo, out_hi} per local row, first local row)");
 
+  // ---- the solver's plan (host only: no device needed) -------------------
+  m.def(
+      "solver_plan",
+      [](const Problem& P, const Block& blk, int comm_size, const SolveOptions& opt, std::optional<int> pe_resident,
+         std::optional<int> pe_steps, std::optional<int> pe_ti, std::optional<int> pe_order, std::optional<int> pe_ti_tune,
+         int cus, int per_cu, int per_cu0, std::optional<bool> resident) {
+        const SolverKnobs knobs{pe_resident, pe_steps, pe_ti, pe_order, pe_ti_tune};
+        SolverPlan pl = plan_solver(P, blk, comm_size, opt, knobs, cus);
+        finish_plan(pl, blk, DeviceFacts{cus, per_cu, per_cu0});
+        // (the resident kernel's own further conditions are the device's: without its answer, the estimate)
+        const bool res = resident ? *resident
+                                  : pl.resident_likely && pl.fused && !pl.sstep && comm_size == 1 && blk.Px * blk.Py == 1;
+        const ChunkPlan ch = plan_chunk(pl, blk, comm_size, opt.chunk, res);
+        py::dict d;
+        d["fused"] = pl.fused;
+        d["steps"] = pl.steps;
+        d["resident_likely"] = pl.resident_likely;
+        d["ti"] = pl.ti;
+        d["ti_query"] = pl.ti_query;
+        d["order"] = pl.order;
+        d["layout"] = pl.lay_name;
+        d["strips"] = pl.geo.strips;
+        d["wave_caps"] = py::make_tuple(pl.wave_caps[0], pl.wave_caps[1]);
+        d["tune_ti"] = pl.tune_ti;
+        d["candidates"] = pl.ti_cands;
+        d["ti_min"] = pl.ti_min;
+        d["npart"] = pl.npart;
+        d["nitems_max"] = pl.nitems_max;
+        d["nslot_cap"] = pl.nslot_cap;
+        d["resident"] = res;
+        d["chunk"] = ch.chunk;
+        d["stream_chunk"] = ch.stream_chunk;
+        d["algo"] = algo_name(pl.fused, pl.steps, res);
+        return d;
+      },
+      py::arg("prob"), py::arg("block"), py::arg("comm_size") = 1, py::arg("opt") = SolveOptions(),
+      py::arg("pe_resident") = py::none(), py::arg("pe_steps") = py::none(), py::arg("pe_ti") = py::none(),
+      py::arg("pe_order") = py::none(), py::arg("pe_ti_tune") = py::none(), py::arg("cus") = 256, py::arg("per_cu") = 0,
+      py::arg("per_cu0") = 0, py::arg("resident") = py::none(),
+      "what a DeviceSolver of this block decides: kernel family, iterations per sweep, rows per item, order, tuning, "
+      "capacities, chunk (pe_*: the parsed PE_* knobs, None: unset; per_cu / per_cu0: resident blocks per CU of the "
+      "applying / deferring sweep; resident: whether the resident kernel runs, None: the estimate)");
+  m.def(
+      "resident_tiling",
+      [](int64_t nx, int64_t ny, int cus) -> py::object {
+        const std::optional<ResidentTiling> t = resident_tiling(nx, ny, cus);
+        if (!t) return py::none();
+        py::dict d;
+        d["strips"] = t->nstrips;
+        d["bands"] = t->ntr;
+        d["rowstart"] = t->rowstart;
+        d["rcap"] = t->rcap;
+        return std::move(d);
+      },
+      py::arg("nx"), py::arg("ny"), py::arg("cus"), "the LDS-resident kernel's tile geometry of a block, or None");
+  m.def(
+      "halo_candidates",
+      [](int steps, bool put_ok, bool push_ok, bool shared_dev, int nheights, std::vector<int> heights,
+         std::optional<std::string> pe_halo, std::optional<int> pe_overlap) {
+        const HaloCandidates hc =
+            halo_candidates(HaloInputs{steps, put_ok, push_ok, shared_dev, nheights, std::move(heights), pe_halo, pe_overlap});
+        py::list l;
+        for (const HaloCandidate& c : hc.list) l.append(py::make_tuple(c.path, c.overlap, c.ti));
+        return py::make_tuple(l, hc.put_ov_late);
+      },
+      py::arg("steps"), py::arg("put_ok") = false, py::arg("push_ok") = false, py::arg("shared_dev") = false,
+      py::arg("nheights") = 1, py::arg("heights") = std::vector<int>{0}, py::arg("pe_halo") = py::none(),
+      py::arg("pe_overlap") = py::none(),
+      "([(path, overlap, rows per item)], put_ov_late): the halo-path candidates in timing order");
+
   // ---- device (HIP / RCCL) ----------------------------------------------
   m.def("device_count", &device_count);
   m.def("set_device", &set_device);
@@ -845,6 +915,43 @@ PYBIND11_MODULE(_native, m) {
             return d;
           },
           "what the solver last asked the layout planner: the keyword arguments of item_layout()")
+      .def_property_readonly(
+          "plan_request",
+          [](const DeviceSolver& s) {
+            const SolverKnobs& kn = s.plan_knobs();
+            py::dict d;
+            d["prob"] = s.problem();
+            d["block"] = s.block();
+            d["comm_size"] = s.comm_size();
+            d["opt"] = s.options();
+            d["pe_resident"] = kn.resident;
+            d["pe_steps"] = kn.steps;
+            d["pe_ti"] = kn.ti;
+            d["pe_order"] = kn.order;
+            d["pe_ti_tune"] = kn.ti_tune;
+            d["cus"] = s.plan_facts().cus;
+            d["per_cu"] = s.plan_facts().per_cu;
+            d["per_cu0"] = s.plan_facts().per_cu0;
+            d["resident"] = s.resident();
+            return d;
+          },
+          "what the solver's plan was made with: the keyword arguments of solver_plan()")
+      .def_property_readonly(
+          "halo_request",
+          [](const DeviceSolver& s) {
+            const HaloInputs& in = s.halo_inputs();
+            py::dict d;
+            d["steps"] = in.steps;
+            d["put_ok"] = in.put_ok;
+            d["push_ok"] = in.push_ok;
+            d["shared_dev"] = in.shared_dev;
+            d["nheights"] = in.nheights;
+            d["heights"] = in.heights;
+            d["pe_halo"] = in.halo;
+            d["pe_overlap"] = in.overlap;
+            return d;
+          },
+          "what the halo-path choice asked for its candidates: the keyword arguments of halo_candidates()")
       .def_property_readonly("layout_waves", [](DeviceSolver& s) { return s.params().lwaves; })
       .def_property_readonly("strips", [](DeviceSolver& s) { return s.params().nstrips; }, "wave strips across the block")
       .def_property_readonly("layout_boundary", &DeviceSolver::layout_boundary,

@@ -28,6 +28,7 @@
 #include <rocprofiler-sdk-roctx/roctx.h>
 
 #include "../hip/kernels.hpp"
+#include "env_knobs.hpp"
 #include "pe/device.hpp"
 #include "solver_internal.hpp"
 
@@ -44,188 +45,201 @@ using detail::Range;
 using detail::secs;
 
 
-// Can the single-sweep kernel run this block?  It needs the fast arithmetic
-// variant and neighbours at least two nodes deep in every split direction
-// (its halo is two rows / columns deep).
-static bool fused_possible(const Problem& P, const Block& b) {
-  const int64_t min_rows = (P.M - 1) / b.Px, min_cols = (P.N - 1) / b.Py;
-  return (b.Px == 1 || min_rows >= 2) && (b.Py == 1 || min_cols >= 2);
+// Compute units of the current device; unchecked: 256 when the runtime does
+// not answer (the plan's resident estimate, before anything is set up).
+static int device_cus(bool checked) {
+  int cus = 256, dev = 0;
+  if (checked) {
+    PE_HIP_CHECK(hipGetDevice(&dev));
+    PE_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+  } else if (hipGetDevice(&dev) == hipSuccess) {
+    (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  }
+  return cus;
 }
 
+// PE_CTOR_TRACE=1: wall time of each construction phase → stderr
+void DeviceSolver::ctor_mark(const char* phase) {
+  if (!ctor_trace_) return;
+  PE_HIP_CHECK(hipDeviceSynchronize());
+  const auto now = clk::now();
+  std::fprintf(stderr, "[pe] ctor %-14s %8.3f ms\n", phase, 1e3 * secs(t_mark_, now));
+  t_mark_ = now;
+}
+
+// The constructor: what to run is the host-only plan's (pe/solver_plan.hpp);
+// the steps below set it up on the device, in the order the job's other ranks
+// run the same collectives.
 DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* comm, const SolveOptions& opt)
     : prob_(prob), blk_(blk), comm_(comm), opt_(opt), kp_(std::make_unique<KParams>()) {
   const auto t_ctor = clk::now();
-  // PE_CTOR_TRACE=1: wall time of each construction phase → stderr
-  const bool ctor_trace = std::getenv("PE_CTOR_TRACE") && std::atoi(std::getenv("PE_CTOR_TRACE")) >= 1;
-  auto t_mark = t_ctor;
-  auto mark = [&](const char* phase) {
-    if (!ctor_trace) return;
-    PE_HIP_CHECK(hipDeviceSynchronize());
-    const auto now = clk::now();
-    std::fprintf(stderr, "[pe] ctor %-14s %8.3f ms\n", phase, 1e3 * secs(t_mark, now));
-    t_mark = now;
-  };
+  const EnvKnobs env = read_env_knobs();
+  ctor_trace_ = env.ctor_trace >= 1;
+  t_mark_ = t_ctor;
   if (!comm_) {
     self_ = std::make_unique<SelfDeviceComm>();
     comm_ = self_.get();
   }
-  if (opt_.algo < 0 || opt_.algo > 4)
-    throw std::invalid_argument("algo: 0 auto, 1 classic, 2 fused, 3 two-step, 4 three-step (got " +
-                                std::to_string(opt_.algo) + ")");
-  // A shifted operator (Problem::shift ≠ 0) runs the classic two-kernel path
-  // on every decomposition: the single-sweep, multi-step and resident kernels
-  // do not carry the shift, and nothing below may launch one of them.
-  check_shift(prob_, "DeviceSolver");
-  const bool shifted = prob_.shift != 0.0;
-  if (shifted && opt_.algo >= 2)
-    throw std::invalid_argument(
-        "algo fused / two-step / three-step: the single-sweep kernels implement the unshifted operator only; a problem "
-        "with shift != 0 (got " + std::to_string(prob_.shift) + ") runs algo auto or classic");
-  const bool can_fuse = !shifted && opt_.variant == 0 && fused_possible(prob_, blk_);
-  if (opt_.algo >= 2 && !can_fuse)
-    throw std::invalid_argument("single-sweep algorithm needs variant 0 and >= 2 rows/columns per split block");
-  fused_ = opt_.algo >= 2 || (opt_.algo == 0 && can_fuse);
-  // Several iterations per sweep (fused2.hip: 2, fused3.hip: 3): single-rank
-  // blocks of ≥ 8 × 8 nodes, or row slabs (Py = 1) over a multi-rank
-  // transport of ≥ 4s rows per rank (the 2s-deep halo comes from one
-  // neighbour and the pushed edge rows are distinct).  Every input is global: every rank
-  // decides the same.  algo 3 / 4 force two / three steps; auto takes three
-  // where it can (PE_STEPS=1/2/3 caps the iterations per sweep).
-  {
-    auto single = [&](int64_t m) { return comm_->size() == 1 && blk_.Px * blk_.Py == 1 && blk_.nx >= m && blk_.ny >= m; };
-    auto slabs = [&](int64_t m) {
-      return comm_->size() > 1 && blk_.Py == 1 && (prob_.M - 1) / blk_.Px >= m && prob_.N - 1 >= m;
-    };
-    // 2-D splits (three-step only): the 6-deep halo through the comm's
-    // exchange — y strips packed after the sweep, then the x rows with their
-    // halo columns (corners) — from blocks of >= 12 rows and columns each
-    auto grid2d = [&](int64_t m) {
-      return comm_->size() > 1 && blk_.Py > 1 && (prob_.M - 1) / blk_.Px >= m && (prob_.N - 1) / blk_.Py >= m;
-    };
-    // virtual ranks on one device (device_solve_group: no comm, a split block;
-    // the group driver exchanges the halos and sums the sweeps' sums)
-    auto vgroup = [&](int64_t m) {
-      return comm_->size() == 1 && blk_.Px * blk_.Py > 1 && (prob_.M - 1) / blk_.Px >= m &&
-             (prob_.N - 1) / blk_.Py >= m;
-    };
-    const bool two_ok = fused_ && (single(8) || slabs(8));
-    const bool three_ok = fused_ && (single(8) || slabs(12) || grid2d(12) || vgroup(12));
-    if (opt_.algo == 3 && !two_ok)
-      throw std::invalid_argument("two-step sweep: single-rank blocks of >= 8 x 8 nodes or row slabs of >= 8 rows");
-    if (opt_.algo == 4 && !three_ok)
-      throw std::invalid_argument(
-          "three-step sweep: single-rank blocks of >= 8 x 8 nodes, row slabs of >= 12 rows or 2-D blocks of >= 12 x 12");
-    // auto: every single-rank block the LDS-resident kernel cannot hold
-    // (1x MI355X, fresh processes, T_solver two-step vs single sweep:
-    // 1600×2400 0.110 vs 0.127 s, 2048² 0.113 vs 0.133, 4096² 0.378 vs 0.584,
-    // 8192² 2.60 vs 3.24, 16384² 13.7 vs 21.7; the resident kernel keeps
-    // ≤ 800×1200: 0.044 vs 0.059 s — profiles/r3_grids_two.txt).  The
-    // estimate mirrors setup_resident's geometry test.
-    bool resident_likely = false;
-    {
-      const char* r = std::getenv("PE_RESIDENT");
-      int ncu = 256, dv = 0;
-      if (hipGetDevice(&dv) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dv);
-      const int64_t ns = (blk_.ny + dev::kFSW - 1) / dev::kFSW;
-      if (!(r && std::atoi(r) == 0) && opt_.variant == 0 && ns <= ncu) {
-        const int64_t ntr = std::max<int64_t>(1, std::min<int64_t>(ncu / ns, blk_.nx / 8));
-        resident_likely = blk_.nx >= 2 * ntr && (blk_.nx + ntr - 1) / ntr <= dev::kResMaxRows &&
-                          ntr * ns <= dev::kResMaxTiles;
-      }
-    }
-    bool auto_ms = slabs(8) || grid2d(12) || vgroup(12) || !resident_likely;
-    int want = 3;
-    if (const char* e = std::getenv("PE_STEPS")) want = std::max(1, std::min(3, std::atoi(e)));
-    steps_ = 1;
-    if (opt_.algo == 3) steps_ = 2;
-    else if (opt_.algo == 4) steps_ = 3;
-    else if (opt_.algo == 0 && auto_ms)
-      steps_ = (want >= 3 && three_ok) ? 3 : (want >= 2 && two_ok) ? 2 : 1;
-    sstep_ = steps_ > 1;
-  }
-
-  mark("start");
+  // 1. plan, stage one: the kernel family, iterations per sweep, rows per
+  //    item and item order (refusals throw here, before anything is allocated)
+  plan_knobs_ = env.plan;
+  plan_ = plan_solver(prob_, blk_, comm_->size(), opt_, env.plan, device_cus(false));
+  fused_ = plan_.fused;
+  steps_ = plan_.steps;
+  sstep_ = plan_.sstep;
+  geo_ = plan_.geo;
+  lay_name_ = plan_.lay_name;
+  ctor_mark("start");
+  // 2. stream and peer diagnostics
   stream_ = acquire_stream();  // (pooled: set_device created one — runtime.cpp)
   device_ = current_device();
-  mark("stream");
-  // Peer access of this rank's device toward every rank's (first cross-device
-  // run diagnostics: the halo push and the in-sweep sums map peers' memory):
-  // 1 / 0 hipDeviceCanAccessPeer, -1 the same physical device, -2 a device this
-  // process cannot see (another node, or masked by HIP_VISIBLE_DEVICES).
-  // Devices are compared by PCI location, not by process-local ordinals, and
-  // gathered 64 ranks per collective (the comms' host scratch size); a failure
-  // leaves the diagnostics empty and never aborts construction.
-  if (comm_->size() > 1) {
-    // key = (host hash << 32) | PCI domain / bus / device: exact in a double
-    // (52 bits), so GPUs of different nodes never compare equal.  Every rank
-    // runs every collective round whatever failed locally (a failure only
-    // turns its own contribution into -1).
-    const int P = comm_->size();
-    auto host_hash = []() -> int64_t {
-      char name[256] = {0};
-      if (gethostname(name, sizeof(name) - 1) != 0) return 0;
-      uint64_t h = 1469598103934665603ull;  // FNV-1a
-      for (const char* c = name; *c; ++c) h = (h ^ uint64_t(uint8_t(*c))) * 1099511628211ull;
-      return int64_t((h ^ (h >> 20) ^ (h >> 40)) & 0xFFFFF);
-    };
-    const int64_t hh = host_hash();
-    auto pci_key = [hh](int dv) -> double {
-      int dom = 0, bus = -1, dev = 0;
-      if (hipDeviceGetAttribute(&dom, hipDeviceAttributePciDomainID, dv) != hipSuccess ||
-          hipDeviceGetAttribute(&bus, hipDeviceAttributePciBusId, dv) != hipSuccess ||
-          hipDeviceGetAttribute(&dev, hipDeviceAttributePciDeviceId, dv) != hipSuccess) {
-        (void)hipGetLastError();
-        return -1.0;
-      }
-      return double((hh << 32) | (int64_t(dom & 0xFFFF) << 16) | (int64_t(bus & 0xFF) << 8) | int64_t(dev & 0xFF));
-    };
-    int mydev = -1, ndev = 0;
-    if (hipGetDevice(&mydev) != hipSuccess || hipGetDeviceCount(&ndev) != hipSuccess) {
-      (void)hipGetLastError();
-      mydev = -1;
-      ndev = 0;
-    }
-    const double mykey = mydev >= 0 ? pci_key(mydev) : -1.0;
-    std::vector<double> keys(size_t(P), -1.0);
-    for (int c0 = 0; c0 < P; c0 += 64) {
-      const int n = std::min(64, P - c0);
-      double chunk[64];
-      for (int i = 0; i < n; ++i) chunk[i] = c0 + i == comm_->rank() ? mykey : -1.0;
-      comm_->host_max(chunk, n, stream_);
-      for (int i = 0; i < n; ++i) keys[size_t(c0 + i)] = chunk[i];
-    }
-    for (int r = 0; r < P; ++r)
-      if (r != comm_->rank() && mykey >= 0 && keys[size_t(r)] == mykey) shared_dev_ = true;
-    std::vector<int> pa(size_t(P), -1);
-    for (int r = 0; r < P && mykey >= 0; ++r) {
-      const double key = keys[size_t(r)];
-      if (key < 0 || key == mykey) continue;
-      int d = -1;
-      for (int i = 0; i < ndev && d < 0; ++i)
-        if (pci_key(i) == key) d = i;
-      if (d < 0) {
-        pa[size_t(r)] = -2;
-        continue;
-      }
-      int can = 0;
-      if (hipDeviceCanAccessPeer(&can, mydev, d) != hipSuccess) {
-        (void)hipGetLastError();
-        can = 0;
-      }
-      pa[size_t(r)] = can;
-    }
-    peer_access_ = std::move(pa);
-  }
+  ctor_mark("stream");
+  if (comm_->size() > 1) peer_diagnostics();
+  // 3. allocation
   KParams& k = *kp_;
   std::memset(&k, 0, sizeof(KParams));
-  const int64_t nx = blk_.nx, ny = blk_.ny;
-  int ti = fused_ ? 16 : 8;  // 8192² sweeps: classic 8 rows, single-sweep 16 (4 halo rows per item)
-  int ti_env = 0;
-  if (const char* e = std::getenv("PE_TI")) ti_env = std::atoi(e);
-  if (ti_env > 0) ti = ti_env;
+  allocate_fields();
+  ctor_mark("fields");
+  allocate_state();
+  // 4. KParams from problem and plan
+  fill_kparams(env);
+  // 5. occupancy of the sweep the plan selected (k.steps / k.ti / k.order), then plan stage two
+  cus_ = device_cus(true);
+  k.ncu = cus_;
+  facts_.cus = cus_;
+  facts_.per_cu = fused_ ? dev::resident_blocks_S(k, 2) : dev::resident_blocks_classic(opt_.variant, prob_.shift != 0.0);
+  facts_.per_cu0 = fused_ ? dev::resident_blocks_S(k, 0) : 0;
+  finish_plan(plan_, blk_, facts_);
+  nslot_cap_ = plan_.nslot_cap;
+  PE_HIP_CHECK(hipMalloc(&partial_, sizeof(double) * (plan_.npart + 8 * int64_t(nslot_cap_))));
+  k.partial = partial_;
+  k.itemsum = fused_ ? partial_ + plan_.npart : nullptr;
+  ctor_mark("buffers");
+  // 6. tables
+  build_tables(geo_.rows_hi, geo_.cols_hi);
+  const bool has[4] = {blk_.has(LEFT), blk_.has(RIGHT), blk_.has(DOWN), blk_.has(UP)};
+  planner_ = std::make_unique<LayoutPlanner>(geo_, blk_.nx, blk_.ny, has, rowcls_host_);
+  ctor_mark("tables");
+  // 7. halo set-up
+  if (env.p2p_timeout_s) put_timeout_s_ = std::max(0.1, *env.p2p_timeout_s);
+  setup_halo_push();
+  setup_halo_put();
+  // 8. layout.  The placement search times the item layout the solve will run
+  // (after apply_layout): its best class then reaches the early-stop rate (8192²
+  // static layout 0.536-0.545 ms vs 0.564-0.567 for the plain walk), so it
+  // stops after 2-3 tries instead of 8 — construction 0.10-0.14 vs 0.15-0.25 s,
+  // the same iteration speed (profiles/r2_bench_psearch.txt).
+  if (comm_->size() > 1) measure_exchange();  // (diagnostic: the comm's exchange, bench JSON)
+  apply_layout(plan_.ti);
+  ctor_mark("items");
+  // 9. placement
+  if (fused_) choose_placement();
+  ctor_mark("placement");
+  // 10. resident
+  setup_resident();
+  ctor_mark("resident");
+  // 11. tuning
+  if (plan_.tune_ti && !resident_) tune_rows_per_item(plan_.ti_cands, plan_.ti);
+  if (fused_ && env.stamps) allocate_stamps();
+  // 12. in-sweep sums
+  setup_in_sweep_sums(env);
+  ctor_mark("ti tuning");
+  // 13. halo path
+  choose_halo_path();
+  ctor_mark("halo path");
+  // 14. chunk
+  const ChunkPlan ch = plan_chunk(plan_, blk_, comm_->size(), opt_.chunk, resident_);
+  chunk_ = ch.chunk;
+  stream_chunk_ = ch.stream_chunk;
+  ctor_mark("tuning+rest");
+  // Graph-replayed solves (--graph): one small pageable copy at construction.
+  // The runtime sets up its pageable-copy path lazily at the first such copy
+  // of the process (≈19 ms, profiles/r2_init_probe.txt) — which a graph
+  // instantiation triggers; this keeps that cost out of the iteration loop (4
+  // µs per iteration at 1600×2400 otherwise).  The eager solve never takes
+  // that path.
+  if (opt_.use_graph) {
+    double h = 0.0;
+    PE_HIP_CHECK(hipMemcpy(partial_, &h, sizeof(double), hipMemcpyHostToDevice));
+  }
+  PE_HIP_CHECK(hipDeviceSynchronize());
+  ctor_s_ = secs(t_ctor, clk::now());
+}
 
-  geo_ = sweep_geometry(nx, ny, steps_, fused_);
-  const int64_t strips = geo_.strips, rows_hi = geo_.rows_hi, cols_hi = geo_.cols_hi;
+// Peer access of this rank's device toward every rank's (first cross-device
+// run diagnostics: the halo push and the in-sweep sums map peers' memory):
+// 1 / 0 hipDeviceCanAccessPeer, -1 the same physical device, -2 a device this
+// process cannot see (another node, or masked by HIP_VISIBLE_DEVICES).
+// Devices are compared by PCI location, not by process-local ordinals, and
+// gathered 64 ranks per collective (the comms' host scratch size); a failure
+// leaves the diagnostics empty and never aborts construction.
+void DeviceSolver::peer_diagnostics() {
+  // key = (host hash << 32) | PCI domain / bus / device: exact in a double
+  // (52 bits), so GPUs of different nodes never compare equal.  Every rank
+  // runs every collective round whatever failed locally (a failure only
+  // turns its own contribution into -1).
+  const int P = comm_->size();
+  auto host_hash = []() -> int64_t {
+    char name[256] = {0};
+    if (gethostname(name, sizeof(name) - 1) != 0) return 0;
+    uint64_t h = 1469598103934665603ull;  // FNV-1a
+    for (const char* c = name; *c; ++c) h = (h ^ uint64_t(uint8_t(*c))) * 1099511628211ull;
+    return int64_t((h ^ (h >> 20) ^ (h >> 40)) & 0xFFFFF);
+  };
+  const int64_t hh = host_hash();
+  auto pci_key = [hh](int dv) -> double {
+    int dom = 0, bus = -1, dev = 0;
+    if (hipDeviceGetAttribute(&dom, hipDeviceAttributePciDomainID, dv) != hipSuccess ||
+        hipDeviceGetAttribute(&bus, hipDeviceAttributePciBusId, dv) != hipSuccess ||
+        hipDeviceGetAttribute(&dev, hipDeviceAttributePciDeviceId, dv) != hipSuccess) {
+      (void)hipGetLastError();
+      return -1.0;
+    }
+    return double((hh << 32) | (int64_t(dom & 0xFFFF) << 16) | (int64_t(bus & 0xFF) << 8) | int64_t(dev & 0xFF));
+  };
+  int mydev = -1, ndev = 0;
+  if (hipGetDevice(&mydev) != hipSuccess || hipGetDeviceCount(&ndev) != hipSuccess) {
+    (void)hipGetLastError();
+    mydev = -1;
+    ndev = 0;
+  }
+  const double mykey = mydev >= 0 ? pci_key(mydev) : -1.0;
+  std::vector<double> keys(size_t(P), -1.0);
+  for (int c0 = 0; c0 < P; c0 += 64) {
+    const int n = std::min(64, P - c0);
+    double chunk[64];
+    for (int i = 0; i < n; ++i) chunk[i] = c0 + i == comm_->rank() ? mykey : -1.0;
+    comm_->host_max(chunk, n, stream_);
+    for (int i = 0; i < n; ++i) keys[size_t(c0 + i)] = chunk[i];
+  }
+  for (int r = 0; r < P; ++r)
+    if (r != comm_->rank() && mykey >= 0 && keys[size_t(r)] == mykey) shared_dev_ = true;
+  std::vector<int> pa(size_t(P), -1);
+  for (int r = 0; r < P && mykey >= 0; ++r) {
+    const double key = keys[size_t(r)];
+    if (key < 0 || key == mykey) continue;
+    int d = -1;
+    for (int i = 0; i < ndev && d < 0; ++i)
+      if (pci_key(i) == key) d = i;
+    if (d < 0) {
+      pa[size_t(r)] = -2;
+      continue;
+    }
+    int can = 0;
+    if (hipDeviceCanAccessPeer(&can, mydev, d) != hipSuccess) {
+      (void)hipGetLastError();
+      can = 0;
+    }
+    pa[size_t(r)] = can;
+  }
+  peer_access_ = std::move(pa);
+}
+
+// The iteration's planes: single-sweep x0, x1 (r and p interleaved by row)
+// and w; classic r, w, p0, p1 in one allocation.
+void DeviceSolver::allocate_fields() {
+  KParams& k = *kp_;
+  const int64_t nx = blk_.nx;
   if (fused_) {
     k.pitch = 2 * geo_.plane;
     k.wpitch = geo_.plane;
@@ -233,7 +247,7 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
     fields_ = static_cast<double*>(field_alloc(sizeof(double) * geo_.xsize));
     xalt_ = static_cast<double*>(field_alloc(sizeof(double) * geo_.xsize));
     walt_ = static_cast<double*>(field_alloc(sizeof(double) * geo_.wsize));
-    mark("field allocs");
+    ctor_mark("field allocs");
     set_fused_fields(fields_, xalt_, walt_);
     hsize_ = std::max<int64_t>(1, nx) * 2 * geo_.hdep;  // y strips: hdep columns of r and p per owned row
   } else {
@@ -247,8 +261,11 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
     k.p[1] = fields_ + 3 * A + blk_.base;
     hsize_ = std::max<int64_t>(1, nx);
   }
-  mark("fields");
-  const int64_t nrow_tab = rows_hi - geo_.tab_lo + 1, ncol_tab = cols_hi - geo_.tab_lo + 1;
+}
+
+// Tables, halo buffers, the device state and its pinned copy, events, the history.
+void DeviceSolver::allocate_state() {
+  const int64_t nrow_tab = geo_.rows_hi - geo_.tab_lo + 1, ncol_tab = geo_.cols_hi - geo_.tab_lo + 1;
   const int64_t ntab = nrow_tab * 4 + ncol_tab * 4;
   PE_HIP_CHECK(hipMalloc(&tables_, sizeof(double) * ntab));
   PE_HIP_CHECK(hipMalloc(&rowcls_, sizeof(int) * nrow_tab * 4));
@@ -263,7 +280,18 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
   PE_HIP_CHECK(hipEventCreateWithFlags(&ev_sync_, hipEventDisableTiming));
   PE_HIP_CHECK(hipEventCreate(&t0_));
   PE_HIP_CHECK(hipEventCreate(&t1_));
+  if (opt_.keep_history) {  // per-iteration ‖Δw‖ on the device (capped at 2²⁴ iterations)
+    kp_->hist_n = std::min<long long>(prob_.iter_cap(), 1LL << 24);
+    PE_HIP_CHECK(hipMalloc(&hist_, sizeof(double) * size_t(std::max<long long>(1, kp_->hist_n))));
+    kp_->hist = hist_;
+  }
+}
 
+// The kernels' parameter block from the problem, the block, the plan and the
+// buffers allocated so far (the item list and the sums' buffers follow).
+void DeviceSolver::fill_kparams(const EnvKnobs& env) {
+  KParams& k = *kp_;
+  const int64_t nrow_tab = geo_.rows_hi - geo_.tab_lo + 1;
   k.fused = fused_ ? 1 : 0;
   k.steps = steps_;
   k.hdep = geo_.hdep;
@@ -273,11 +301,11 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
   // 1600×2400 T_iterate −0.8-1.5 % at PE_PRIO=10, but the 2-rank blocks of
   // 2048² / 1600×2400 +2-7 % (20.2 vs 18.9 µs per iteration), 8192² −4-6 %
   // it/s, the 8-rank slab and 4×2 blocks neutral — profiles/r5_prio.txt
-  k.prio = std::getenv("PE_PRIO") ? std::max(0, std::min(20, std::atoi(std::getenv("PE_PRIO")))) : 0;
-  k.stage = !(std::getenv("PE_STAGE") && std::atoi(std::getenv("PE_STAGE")) == 0);
+  k.prio = env.prio;
+  k.stage = env.stage;
   k.xorg = geo_.xorg;
-  k.nx = nx;
-  k.ny = ny;
+  k.nx = blk_.nx;
+  k.ny = blk_.ny;
   k.M = prob_.M;
   k.N = prob_.N;
   k.gi0 = blk_.i0 - 1;
@@ -316,35 +344,17 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
   // only) makes the host believe the device never finishes (the watchdog
   // must fire); PE_WATCHDOG_S sets the
   // no-progress limit of the host loop.
-  if (const char* e = std::getenv("PE_FAULT_INJECT")) {
-    const std::string f = e;
-    if (f.rfind("nan@iter:", 0) == 0) k.fault_iter = std::atoll(f.c_str() + 9);
-    if (f.rfind("zero@iter:", 0) == 0) k.fault_zero = std::atoll(f.c_str() + 10);
-    if (f == "stall") fault_stall_ = true;
-    // stall@rank:R — only rank R hangs (its watchdog fires and aborts the
-    // communicator; the peers then see the transport fail, not a hang)
-    if (f.rfind("stall@rank:", 0) == 0 && std::atoi(f.c_str() + 11) == blk_.rank) fault_stall_ = true;
-    // slow@rank:R,us:X — rank R's sweeps idle X µs before their cross-rank
-    // sum (the peers' T_MPI must show it: iterations × X)
-    if (f.rfind("slow@rank:", 0) == 0 && std::atoi(f.c_str() + 10) == blk_.rank) {
-      const size_t u = f.find("us:");
-      k.slow_ticks = u == std::string::npos ? 0 : (long long)(std::atof(f.c_str() + u + 3) * 100.0);
-    }
-    // drift@iter:K[,amp:X] — w(M/2, N/2) += X behind the recurrence's back
-    // (the end-of-solve residual check must see the gap; three-step restarts)
-    if (f.rfind("drift@iter:", 0) == 0) {
-      fault_drift_ = std::atoll(f.c_str() + 11);
-      const size_t u = f.find("amp:");
-      if (u != std::string::npos) fault_drift_amp_ = std::atof(f.c_str() + u + 4);
-    }
+  const FaultInject& fi = env.fault;
+  k.fault_iter = fi.nan_iter;
+  k.fault_zero = fi.zero_iter;
+  fault_stall_ = fi.stall || fi.stall_rank == blk_.rank;
+  if (fi.slow_rank == blk_.rank) k.slow_ticks = fi.slow_ticks;
+  if (fi.drift) {
+    fault_drift_ = fi.drift_iter;
+    if (fi.drift_amp) fault_drift_amp_ = *fi.drift_amp;
   }
-  if (const char* e = std::getenv("PE_RESID_GAP")) gap_bound_ = std::atof(e);
-  if (const char* e = std::getenv("PE_WATCHDOG_S")) watchdog_s_ = std::atof(e);
-  if (opt_.keep_history) {  // per-iteration ‖Δw‖ on the device (capped at 2²⁴ iterations)
-    k.hist_n = std::min<long long>(prob_.iter_cap(), 1LL << 24);
-    PE_HIP_CHECK(hipMalloc(&hist_, sizeof(double) * size_t(std::max<long long>(1, k.hist_n))));
-    k.hist = hist_;
-  }
+  if (env.resid_gap) gap_bound_ = *env.resid_gap;
+  if (env.watchdog_s) watchdog_s_ = *env.watchdog_s;
   // Work decomposition: wave strips (128 columns classic, 124 output
   // columns single-sweep) × `ti`-row chunks, dealt round-robin (chunk-major)
   // to a persistent grid of ~16 waves per CU, so the waves running at any
@@ -354,90 +364,9 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
   // Persistent grid: exactly the resident waves (a second partial round of
   // blocks would run after the first finishes — a tail of up to one item
   // per wave).
-  int cus = 256;
-  {
-    int dev = 0;
-    PE_HIP_CHECK(hipGetDevice(&dev));
-    PE_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  }
-  cus_ = cus;
-  k.ncu = cus;
-  // rows per item and item order first: they select the sweep kernel variant
-  // whose occupancy sizes the grid
-  const double npts = double(nx) * double(ny);
-  const bool big = npts >= double(1 << 24), huge = npts > double(1 << 26);
-  // Single-sweep item order and rows per item (profiles/r2_order.txt,
-  // profiles/r2_bench_static.txt; one memory placement per comparison):
-  //  * blocks > 2²⁶ nodes (16384²): the per-XCD dynamic queue, 18 rows —
-  //    with ≈45 items per wave a static layout's per-wave durations drift
-  //    apart (2150 vs 2195 µs per iteration static 24 rows);
-  //  * 2²⁴ .. 2²⁶ (8192², the 2-rank 8192² block): the cost-aware static LPT
-  //    layout, 24 rows, untuned — no item-sum reduction kernel, no queue
-  //    atomics, and with 6-12 items per wave its load is even (8192²: 540-542
-  //    vs 548 µs dynamic; 2-rank block 315-318 vs 333);
-  //  * smaller blocks: static, rows per item tuned below (small blocks: the
-  //    queue's pull latency and the reduction launch never pay — 4-rank block
-  //    155-159 vs 188 µs, 2400×3200 80 vs 109).
-  if (fused_ && ti_env == 0) ti = huge ? 18 : big ? 24 : 10;
-  k.order = (fused_ && huge) ? 3 : 0;
-  if (sstep_) {  // static LPT layout only; taller items (2·hdep pipeline-fill rows each)
-    // (three-step beyond 2²⁶ nodes: 128 rows — 16384² 978 vs 999 µs/iteration
-    // at 80, one placement, profiles/r3_ti_final.txt)
-    if (ti_env == 0) ti = steps_ >= 3 ? (huge ? 448 : npts >= double(1 << 25) ? 112 : big ? 80 : 48) : (big ? 40 : 24);
-    ti = std::max(4, std::min(ti, steps_ >= 3 ? dev::kTImax3 : dev::kTImax2));
-    k.order = 0;
-  }
-  if (const char* e = std::getenv("PE_ORDER")) k.order = std::atoi(e);
-  if (!fused_ && k.order > 1) k.order = 0;
-  if (sstep_) k.order = 0;
-  k.ti = (fused_ && ti_env < 0) ? 1 << 20 : ti;  // bands mode: long items → general kernel
-  int per_cu = fused_ ? dev::resident_blocks_S(k, 2) : dev::resident_blocks_classic(opt_.variant, prob_.shift != 0.0);
-  if (per_cu <= 0) per_cu = 4;
-  int wave_cap = cus * per_cu * dev::kWPB;
-  // PE_TI=-1 (single-sweep): "bands" — one item per resident wave, the rows
-  // split into wave_cap/nstrips bands that the waves of a band march down
-  // together (halo rows re-read once per band, perfect balance).
-  if (fused_ && ti_env < 0) {
-    const int64_t bands = std::max<int64_t>(1, wave_cap / std::max<int64_t>(1, strips));
-    ti = int((nx + bands - 1) / bands);
-  }
-  k.nstrips = int(strips);
-  int wave_cap0 = wave_cap;
-  if (fused_) {
-    const int per0 = dev::resident_blocks_S(k, 0);
-    if (per0 > 0) wave_cap0 = cus * per0 * dev::kWPB;
-  }
-  wave_caps_[0] = wave_cap;
-  wave_caps_[1] = wave_cap0;
-  // Rows per item: fixed (PE_TI, the classic path, blocks ≥ 2²⁴ nodes), or
-  // tuned among ti_candidates() for smaller static sweeps.
-  tune_ti_ = fused_ && ti_env == 0 && k.order == 0 && npts >= double(1 << 20) && !big;
-  // (from 2²⁰ nodes: a tuned layout depends on the timings, so two
-  // constructions of a smaller block — a checkpointed solve and its resume —
-  // could lay it out differently and the resume would not be bitwise; round 5
-  // tuned from 2¹⁷ and test_three_step_checkpoint_resume_bitwise caught it)
-  if (sstep_) tune_ti_ = ti_env == 0 && npts >= double(1 << 20) && npts < double(1 << 25);
-  // Three-step static layout by block size, one placement per block
-  // (tools/layout_probe.py, profiles/r4_layout2.txt, µs per iteration): the
-  // LPT layout of whole items for ≥ 5·10⁷ nodes (8192²: 253 vs 260 filling,
-  // 275 equal-cost), the filling layout from 2.5·10⁷ (the 2-rank 8192² block:
-  // 137 vs 145-147), the equal-cost one below (4-rank block 83.4-84.2 vs
-  // 87.4-87.9 LPT, 8-rank block 45.1 vs 47.6-49.6); tuned blocks also try the
-  // other two at their best rows per item.
-  if (steps_ >= 3) lay_name_ = npts >= 5e7 ? "lpt" : npts >= 2.5e7 ? "fill" : "equal";
-  if (const char* e = std::getenv("PE_TI_TUNE")) tune_ti_ = tune_ti_ && std::atoi(e) != 0;
-  std::vector<int> ti_cands;
-  if (tune_ti_) ti_cands = ti_candidates(geo_, nx, ny, std::min(wave_cap, wave_cap0));
-  const int ti_min = tune_ti_ ? ti_cands.front() : ti;
-  // block partials: interior grid, then (overlap) the boundary grid after it
-  const int64_t npart = 8 * std::max<int64_t>(2 * int64_t(std::max(wave_cap, wave_cap0) / dev::kWPB + 1), 4096);
-  // item-sum slots: one per item (static sweeps split heavy items into up to
-  // ti pieces: the planner)
-  const int64_t nitems_max = strips * ((nx + ti_min - 1) / ti_min);
-  nslot_cap_ = fused_ ? int((k.order == 0 ? ti + 1 : 2) * nitems_max + 64) : 0;
-  PE_HIP_CHECK(hipMalloc(&partial_, sizeof(double) * (npart + 8 * int64_t(nslot_cap_))));
-  k.partial = partial_;
-  k.itemsum = fused_ ? partial_ + npart : nullptr;
+  k.order = plan_.order;
+  k.ti = plan_.ti_query;
+  k.nstrips = int(geo_.strips);
   k.ih1sq = 1.0 / k.h1sq;
   k.ih2sq = 1.0 / k.h2sq;
   k.D_in = (1.0 + 1.0) / k.h1sq + (1.0 + 1.0) / k.h2sq;
@@ -451,46 +380,29 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
     k.dinv_in = 1.0 / shifted_diag((1.0 + 1.0) * k.ih1sq + (1.0 + 1.0) * k.ih2sq, k.shift);
     k.dinv_out = 1.0 / shifted_diag((k.inv_eps + k.inv_eps) * k.ih1sq + (k.inv_eps + k.inv_eps) * k.ih2sq, k.shift);
   }
-  mark("buffers");
-  build_tables(rows_hi, cols_hi);
-  const bool has[4] = {blk_.has(LEFT), blk_.has(RIGHT), blk_.has(DOWN), blk_.has(UP)};
-  planner_ = std::make_unique<LayoutPlanner>(geo_, nx, ny, has, rowcls_host_);
-  mark("tables");
-  if (const char* e = std::getenv("PE_P2P_TIMEOUT_S")) put_timeout_s_ = std::max(0.1, std::atof(e));
-  setup_halo_push();
-  setup_halo_put();
-  // The placement search times the item layout the solve will run (after
-  // apply_layout): its best class then reaches the early-stop rate (8192²
-  // static layout 0.536-0.545 ms vs 0.564-0.567 for the plain walk), so it
-  // stops after 2-3 tries instead of 8 — construction 0.10-0.14 vs 0.15-0.25 s,
-  // the same iteration speed (profiles/r2_bench_psearch.txt).
-  if (comm_->size() > 1) measure_exchange();  // (diagnostic: the comm's exchange, bench JSON)
-  apply_layout(ti);
-  mark("items");
-  if (fused_) choose_placement();
-  mark("placement");
-  setup_resident();
-  mark("resident");
-  if (tune_ti_ && !resident_) tune_rows_per_item(ti_cands, ti);
-  if (fused_ && std::getenv("PE_STAMPS") && std::atoi(std::getenv("PE_STAMPS")) == 1) {
-    const size_t nw = size_t(dev::kWPB) * size_t(std::max(k.nblocks, k.nblocks0));
-    nstamps_ = 4 * size_t(nslot_cap_) + 2 * nw + 32 * nw + 8;  // (+8 whole-grid stamps: three-step sweep)
-    PE_HIP_CHECK(hipMalloc(&stamps_, sizeof(unsigned long long) * nstamps_));
-    PE_HIP_CHECK(hipMemsetAsync(stamps_, 0, sizeof(unsigned long long) * nstamps_, stream_));
-    k.stamps = stamps_;
-    k.stamps2 = stamps_ + nstamps_ - 32 * nw;  // the last 32 × waves entries (the 8 grid stamps before them)
-  }
-  // In-sweep cross-rank reduction (after the placement search, whose sweeps
-  // are local and differ in number between ranks).  PE_XR=0 keeps the
-  // separate allreduce launch.
+}
+
+// PE_STAMPS=1: the sweeps' diagnostic timeline (KParams::stamps)
+void DeviceSolver::allocate_stamps() {
+  KParams& k = *kp_;
+  const size_t nw = size_t(dev::kWPB) * size_t(std::max(k.nblocks, k.nblocks0));
+  nstamps_ = 4 * size_t(nslot_cap_) + 2 * nw + 32 * nw + 8;  // (+8 whole-grid stamps: three-step sweep)
+  PE_HIP_CHECK(hipMalloc(&stamps_, sizeof(unsigned long long) * nstamps_));
+  PE_HIP_CHECK(hipMemsetAsync(stamps_, 0, sizeof(unsigned long long) * nstamps_, stream_));
+  k.stamps = stamps_;
+  k.stamps2 = stamps_ + nstamps_ - 32 * nw;  // the last 32 × waves entries (the 8 grid stamps before them)
+}
+
+// In-sweep cross-rank reduction (after the placement search, whose sweeps
+// are local and differ in number between ranks).  PE_XR=0 keeps the
+// separate allreduce launch.
+void DeviceSolver::setup_in_sweep_sums(const EnvKnobs& env) {
+  KParams& k = *kp_;
   xr_status_ = comm_->size() < 2 ? "none: one rank" : "allreduce launch (" + comm_->name() + ")";
-  if (fused_ && comm_->size() > 1 && comm_->peer_sum()) {
-    const char* e = std::getenv("PE_XR");
-    if (!(e && std::atoi(e) == 0)) {
-      k.xr = *comm_->peer_sum();
-      k.xr.wait_acc = &st_->xr_wait;  // T_MPI of the in-sweep sum (DevState::xr_wait, xr_n)
-      xr_status_ = "in-sweep P2P over xGMI";
-    }
+  if (fused_ && comm_->size() > 1 && comm_->peer_sum() && env.xr) {
+    k.xr = *comm_->peer_sum();
+    k.xr.wait_acc = &st_->xr_wait;  // T_MPI of the in-sweep sum (DevState::xr_wait, xr_n)
+    xr_status_ = "in-sweep P2P over xGMI";
   }
   if (fused_ && comm_->size() > 1 && !comm_->peer_sum()) xr_status_ += "; P2P set-up " + p2p_setup_status();
   // The push's pointers (its kernel variant runs when choose_halo_path picks
@@ -509,37 +421,6 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
     k.hrecv = hrecv_;
   }
   k.push = 0;
-  mark("ti tuning");
-  choose_halo_path();
-  mark("halo path");
-
-  // Iterations per host check: aim for ~0.5 ms of device work per chunk.
-  const double pts = double(nx) * double(ny);
-  const double t_iter = pts * (sstep_ ? 48.0 / steps_ : fused_ ? 48.0 : 64.0) / 4.5e12 + 6e-6 + (comm_->size() > 1 ? 40e-6 : 0.0);
-  int c = int(0.5e-3 / t_iter);
-  c = std::max(8, std::min(128, c));
-  c += c & 1;
-  if (sstep_) c = (c + 2 * steps_ - 1) / (2 * steps_) * (2 * steps_);  // whole sweeps, an even number of them (graph parity)
-  stream_chunk_ = opt_.chunk > 0 ? (opt_.chunk + (opt_.chunk & 1)) : c;
-  if (resident_) c = 512;  // one launch per chunk (≈ 5 ms of iterations at 800×1200)
-  chunk_ = opt_.chunk > 0 ? (opt_.chunk + (opt_.chunk & 1)) : c;
-  if (sstep_) {
-    chunk_ = (chunk_ + 2 * steps_ - 1) / (2 * steps_) * (2 * steps_);
-    stream_chunk_ = chunk_;
-  }
-  mark("tuning+rest");
-  // Graph-replayed solves (--graph): one small pageable copy at construction.
-  // The runtime sets up its pageable-copy path lazily at the first such copy
-  // of the process (≈19 ms, profiles/r2_init_probe.txt) — which a graph
-  // instantiation triggers; this keeps that cost out of the iteration loop (4
-  // µs per iteration at 1600×2400 otherwise).  The eager solve never takes
-  // that path.
-  if (opt_.use_graph) {
-    double h = 0.0;
-    PE_HIP_CHECK(hipMemcpy(partial_, &h, sizeof(double), hipMemcpyHostToDevice));
-  }
-  PE_HIP_CHECK(hipDeviceSynchronize());
-  ctor_s_ = secs(t_ctor, clk::now());
 }
 
 void DeviceSolver::relayout(int ti, int order) {
@@ -1398,7 +1279,7 @@ SolveResult DeviceSolver::solve() {
   const auto t_start = clk::now();
   SolveResult res;
   res.backend = "hip";
-  res.algo = resident_ ? "resident" : steps_ == 3 ? "three-step" : steps_ == 2 ? "two-step" : fused_ ? "fused" : "classic";
+  res.algo = algo_name(fused_, steps_, resident_);
   res.Px = blk_.Px;
   res.Py = blk_.Py;
   // T_solver spans construction (allocation, tables, placement search) like
@@ -1428,7 +1309,7 @@ SolveResult DeviceSolver::solve() {
   // (all of them with opt_.timing); no host sync beyond the per-chunk state
   // read the loop does anyway.
   int sample_every = 8, sample_iters = 2;
-  if (const char* e = std::getenv("PE_TIMER_SAMPLE")) sample_every = std::max(0, std::atoi(e));
+  if (const std::optional<int> e = read_env_knobs().timer_sample) sample_every = std::max(0, *e);
   if (opt_.timing) {
     sample_every = 1;
     sample_iters = chunk_;
@@ -1961,7 +1842,7 @@ SolveResult device_solve_group(const Problem& P, const ProcessGrid& pg, const So
   PE_HIP_CHECK(hipFree(dp));
   for (auto& e : ev) PE_HIP_CHECK(hipEventDestroy(e));
   res.backend = "hip-group";
-  res.algo = steps == 3 ? "three-step" : steps == 2 ? "two-step" : fused ? "fused" : "classic";
+  res.algo = algo_name(fused, steps, false);
   res.Px = pg.Px;
   res.Py = pg.Py;
   res.t.solver = secs(t_start, clk::now());

@@ -20,6 +20,7 @@
 #include <rocprofiler-sdk-roctx/roctx.h>
 
 #include "../hip/kernels.hpp"
+#include "env_knobs.hpp"
 #include "pe/device.hpp"
 #include "solver_internal.hpp"
 
@@ -45,15 +46,15 @@ using detail::secs;
 // decision (PE_HALO=exchange / put: never).
 void DeviceSolver::setup_halo_push() {
   push_ = push_ok_ = false;
-  const char* hm = std::getenv("PE_HALO");
-  const bool allowed = !hm || std::string(hm) == "push";
+  const EnvKnobs env = read_env_knobs();
+  const bool allowed = !env.halo || *env.halo == "push";
   // PE_PUSH_LOOPBACK=1 (diagnostic, tools/block_probe.py on one GPU): the
   // push kernel's work without peers — every push lands in this rank's own
   // receive buffer and the halo rows are read back from it (wrong values,
   // the real stores and loads), so a row slab's per-rank time includes what
   // the 8-GPU job's push kernel does
-  if (const char* e = std::getenv("PE_PUSH_LOOPBACK"); allowed && e && std::atoi(e) == 1 && comm_->size() > 1 &&
-                                                       fused_ && blk_.Py == 1 && (prob_.M - 1) / blk_.Px >= 2 * geo_.hdep) {
+  if (allowed && env.push_loopback && comm_->size() > 1 && fused_ && blk_.Py == 1 &&
+      (prob_.M - 1) / blk_.Px >= 2 * geo_.hdep) {
     const size_t bytes = sizeof(double) * 4 * size_t(geo_.hdep) * size_t(kp_->pitch);
     void* buf = nullptr;
     PE_HIP_CHECK(hipExtMallocWithFlags(&buf, bytes, hipDeviceMallocFinegrained));
@@ -72,8 +73,8 @@ void DeviceSolver::setup_halo_push() {
   push_status_ = "off: slabs thinner than 2 halo depths";
   if ((prob_.M - 1) / blk_.Px < 2 * geo_.hdep) return;  // edge rows 1..h and nx-h+1..nx distinct
   push_status_ = "off: PE_XR=0";
-  if (const char* e = std::getenv("PE_XR"); e && std::atoi(e) == 0) return;
-  push_status_ = std::string("off: PE_HALO=") + (hm ? hm : "");
+  if (!env.xr) return;
+  push_status_ = std::string("off: PE_HALO=") + env.halo.value_or("");
   if (!allowed) return;
   push_status_ = "fallback: the receive buffers could not be mapped on every rank";
   const size_t bytes = sizeof(double) * 4 * size_t(geo_.hdep) * size_t(kp_->pitch);  // [parity][side][hdep rows]
@@ -126,9 +127,7 @@ void DeviceSolver::setup_halo_push() {
     PE_HIP_CHECK(hipStreamSynchronize(stream_));
     PE_HIP_CHECK(hipFree(bad));
     // PE_FAULT_INJECT=pushtest@rank:R — rank R's check fails (fallback test)
-    if (const char* e = std::getenv("PE_FAULT_INJECT"); e && std::string(e).rfind("pushtest@rank:", 0) == 0 &&
-                                                        std::atoi(e + 14) == blk_.rank)
-      hbad = 1;
+    if (env.fault.pushtest_rank == blk_.rank) hbad = 1;
     double fail[1] = {hbad != 0 ? 1.0 : 0.0};
     if (hbad) std::fprintf(stderr, "[pe] rank %d: halo-push self-test: %d wrong values received\n", blk_.rank, hbad);
     comm_->host_max(fail, 1, stream_);
@@ -160,12 +159,11 @@ void DeviceSolver::setup_halo_push() {
 // on one device.  PE_HALO=exchange / push: off.
 void DeviceSolver::setup_halo_put() {
   put_ = put_ok_ = false;
-  const char* hm = std::getenv("PE_HALO");
-  const bool allowed = !hm || std::string(hm) == "put";
-  const char* lb = std::getenv("PE_PUT_LOOPBACK");
-  put_loop_ = lb && std::atoi(lb) == 1;
+  const EnvKnobs env = read_env_knobs();
+  const bool allowed = !env.halo || *env.halo == "put";
+  put_loop_ = env.put_loopback;
   put_status_ = comm_->size() < 2 ? "off: one rank" : !fused_ ? "off: classic path" : !allowed
-                ? std::string("off: PE_HALO=") + hm : (!put_loop_ && !comm_->peer_sum())
+                ? std::string("off: PE_HALO=") + *env.halo : (!put_loop_ && !comm_->peer_sum())
                 ? "off: no P2P transport (" + p2p_setup_status() + ")" : "";
   if (!put_status_.empty()) return;
   // inbox slot: the largest message of a phase — y strips (2·hdep values per
@@ -252,9 +250,7 @@ void DeviceSolver::setup_halo_put() {
     PE_HIP_CHECK(hipFree(codes));
     PE_HIP_CHECK(hipFree(bad));
     // PE_FAULT_INJECT=puttest@rank:R — rank R's check fails (fallback test)
-    if (const char* e = std::getenv("PE_FAULT_INJECT"); e && std::string(e).rfind("puttest@rank:", 0) == 0 &&
-                                                        std::atoi(e + 13) == blk_.rank)
-      hbad = 1;
+    if (env.fault.puttest_rank == blk_.rank) hbad = 1;
     if (hbad) std::fprintf(stderr, "[pe] rank %d: halo-put self-test: %d wrong values received\n", blk_.rank, hbad);
     double fail[1] = {hbad != 0 ? 1.0 : 0.0};
     comm_->host_max(fail, 1, stream_);
@@ -331,7 +327,7 @@ void DeviceSolver::apply_halo_path(const std::string& path, bool overlap, bool l
     const auto t0 = clk::now();
     const double up0 = copy_setup_s_;
     apply_layout(nti);
-    if (live && std::getenv("PE_CTOR_TRACE") && std::atoi(std::getenv("PE_CTOR_TRACE")) >= 2)
+    if (live && read_env_knobs().ctor_trace >= 2)
       std::fprintf(stderr, "[pe] halo path re-layout %s at %d rows: %6.3f ms (list upload %6.3f ms)\n",
                    overlap_ ? "overlap" : "plain", kp_->ti, 1e3 * secs(t0, clk::now()), 1e3 * (copy_setup_s_ - up0));
   }
@@ -374,12 +370,7 @@ void DeviceSolver::choose_halo_path() {
     apply_halo_path("exchange", false);
     return;
   }
-  const char* hm = std::getenv("PE_HALO");
-  const char* ov = std::getenv("PE_OVERLAP");
-  // (the two-step sweep has no boundary-item signal; every rank decides this
-  // from global inputs — a rank without neighbours still takes part, its
-  // overlap is simply off in apply_layout)
-  const bool ov_able = !sstep_ || steps_ >= 3;
+  const EnvKnobs env = read_env_knobs();
   struct Cand {
     std::string path;
     bool ov;
@@ -387,10 +378,6 @@ void DeviceSolver::choose_halo_path() {
     int ti;  // rows per item (0: the construction's)
   };
   std::vector<Cand> cands;
-  // The overlapped candidates run at each of the rows-per-item tuning's three
-  // best heights (its boundary-first layout ranks them differently); with the
-  // exchange among the candidates the put's overlap runs only at the height
-  // the exchange's overlap timed best (the halo path does not move that rank).
   const int ti0 = kp_->ti;
   std::vector<int> heights = ti_alt_.empty() ? std::vector<int>{ti0} : ti_alt_;
   {  // every rank times as many candidates (and calls host_max as often): each
@@ -400,39 +387,15 @@ void DeviceSolver::choose_halo_path() {
     comm_->host_max(v, 1, stream_);
     heights.resize(size_t(std::max(1.0, -v[0])));
   }
-  auto add = [&](const char* path, bool o) {
-    if (o && !ov_able) return;
-    if (ov && (std::atoi(ov) != 0) != o) return;
-    if (!o) {
-      cands.push_back(Cand{path, o, 0.0, 0});
-      return;
-    }
-    for (int h : heights) cands.push_back(Cand{path, o, 0.0, h});
-  };
-  // (the plain-layout candidates first, then the overlapped ones, height by height)
-  const bool ex_ok = !hm || std::string(hm) == "exchange";
-  if (ex_ok) add("exchange", false);
-  if (put_ok_) add("put", false);
-  if (push_ok_ && !(ov && std::atoi(ov) != 0)) cands.push_back(Cand{"push", false, 0.0, 0});
-  if (ex_ok) add("exchange", true);
-  // (not when ranks share a GPU — test jobs: put blocks spinning on the halo
-  // stream under another process's persistent sweep can starve it of CUs; a
-  // 6-process 2×3 job on one GPU stalled past 3 minutes, round 6)
-  const bool put_ov_forced = hm && std::string(hm) == "put" && ov && std::atoi(ov) != 0;
-  const bool put_ov = put_ok_ && (!shared_dev_ || put_ov_forced) && ov_able && !(ov && std::atoi(ov) == 0);
-  const bool put_ov_late = put_ov && ex_ok && !cands.empty() && cands.back().ov;  // (after the exchange's heights)
-  if (put_ov && !put_ov_late) add("put", true);
-  if (cands.empty()) {  // (the forced path is not available here: the exchange, at every height when overlapped)
-    if (ov && std::atoi(ov) != 0 && ov_able) {
-      for (int h : heights) cands.push_back(Cand{"exchange", true, 0.0, h});
-    } else {
-      cands.push_back(Cand{"exchange", false, 0.0, 0});
-    }
-  }
+  // the ordered list, the same on every rank (pe/solver_plan.hpp: a function of these inputs only)
+  halo_in_ = HaloInputs{steps_, put_ok_, push_ok_, shared_dev_, int(heights.size()), heights, env.halo, env.overlap};
+  const HaloCandidates hc = pe::halo_candidates(halo_in_);
+  for (const HaloCandidate& c : hc.list) cands.push_back(Cand{c.path, c.overlap, 0.0, c.ti});
+  const bool put_ov_late = hc.put_ov_late;
   auto name = [](const Cand& c) { return c.path + (c.ov ? "+overlap" : ""); };
   // (an overlap at another height than the tuned one is reported as "exchange+overlap @96")
   auto label = [&](const Cand& c) { return name(c) + (c.ov && c.ti != ti0 ? " @" + std::to_string(c.ti) : std::string()); };
-  const bool tune = !(std::getenv("PE_HALO_TUNE") && std::atoi(std::getenv("PE_HALO_TUNE")) == 0);
+  const bool tune = env.halo_tune;
   if ((cands.size() == 1 && !put_ov_late) || !tune) {
     apply_halo_path(cands[0].path, cands[0].ov, false, cands[0].ti);
     halo_path_ = name(cands[0]) + (cands.size() == 1 ? " (only candidate)" : " (PE_HALO_TUNE=0)");
@@ -446,7 +409,7 @@ void DeviceSolver::choose_halo_path() {
   kp_->check_tol = 0;
   // (PE_CTOR_TRACE=1: rank 0's candidate times; 2: every rank's, with the
   // host-side split of each candidate into switch and timing)
-  const int trace_lvl = std::getenv("PE_CTOR_TRACE") ? std::atoi(std::getenv("PE_CTOR_TRACE")) : 0;
+  const int trace_lvl = env.ctor_trace;
   const bool trace = trace_lvl >= 2 || (trace_lvl == 1 && blk_.rank == 0);
   const auto t_reset = clk::now();
   reset();

@@ -11,6 +11,7 @@
 #include <rocprofiler-sdk-roctx/roctx.h>
 
 #include "../hip/kernels.hpp"
+#include "env_knobs.hpp"
 #include "pe/device.hpp"
 #include "solver_internal.hpp"
 
@@ -37,14 +38,9 @@ static_assert(sizeof(Entry) == sizeof(int2) && offsetof(Entry, x) == offsetof(in
 ItemLayout DeviceSolver::plan_layout(int ti, bool want_overlap, bool push, LayoutRequest* asked) {
   const bool nb = blk_.has(LEFT) || blk_.has(RIGHT) || blk_.has(DOWN) || blk_.has(UP);
   const bool overlap = want_overlap && fused_ && (!sstep_ || steps_ >= 3) && comm_->size() > 1 && nb && !push;
-  LayoutRequest rq{ti, kp_->order, overlap, lay_name_, {wave_caps_[0], wave_caps_[1]}, std::min(wave_caps_[0], wave_caps_[1]),
-                   cus_, 8, nslot_cap_, {}};
-  if (const char* e = std::getenv("PE_LAYOUT")) rq.knobs.force_layout = *e ? e : "lpt";  // (anything but equal / fill: lpt)
-  if (const char* e = std::getenv("PE_YOUNG")) rq.knobs.young = std::max(0.5, std::atof(e));
-  if (const char* e = std::getenv("PE_WPERM")) rq.knobs.wperm = std::atoi(e);
-  // timing experiments (PE_OV_DEBUG bits): 2 serial streams, 4 natural item order (no boundary-first list)
-  if (const char* e = std::getenv("PE_OV_DEBUG")) rq.knobs.ov_debug = std::atoi(e);
-  if (const char* e = std::getenv("PE_CTOR_TRACE")) rq.knobs.trace = std::atoi(e);
+  LayoutRequest rq{ti, kp_->order, overlap, lay_name_, {plan_.wave_caps[0], plan_.wave_caps[1]},
+                   std::min(plan_.wave_caps[0], plan_.wave_caps[1]),
+                   cus_, 8, nslot_cap_, read_env_knobs().layout};
   if (asked) *asked = rq;
   if (!lay_cache_on_) return planner_->build(rq);
   const auto key = std::make_tuple(ti, overlap, lay_name_);
@@ -104,7 +100,8 @@ void DeviceSolver::apply_layout(int ti) {
 // the fastest kept; every rank tunes its own block.
 void DeviceSolver::tune_rows_per_item(const std::vector<int>& cands, int ti) {
   Range range("pe.tune_rows_per_item");
-  const bool ctor_trace = std::getenv("PE_CTOR_TRACE") && std::atoi(std::getenv("PE_CTOR_TRACE")) >= 1;
+  const EnvKnobs env = read_env_knobs();
+  const bool ctor_trace = env.ctor_trace >= 1;
   float best_ms = 0.f;
   int best = ti;
   // one candidate: S_0 + 1 + kTimed local sweeps on real data, the last
@@ -175,7 +172,7 @@ void DeviceSolver::tune_rows_per_item(const std::vector<int>& cands, int ti) {
   };
   std::vector<Tried> tried;
   for (size_t i = 0; i < ti_rows_.size(); ++i) tried.push_back(Tried{ti_rows_[i], lay_name_, ti_ms_[i] * float(kTimed)});
-  if (steps_ >= 3 && !std::getenv("PE_LAYOUT")) {
+  if (steps_ >= 3 && env.layout.force_layout.empty()) {  // (PE_LAYOUT unset)
     const std::string base = lay_name_;
     std::vector<Trial> tr;
     for (const char* alt : {"equal", "fill", "lpt"})
@@ -224,33 +221,26 @@ void DeviceSolver::tune_rows_per_item(const std::vector<int>& cands, int ti) {
   lay_cache_.clear();
 }
 
-// LDS-resident geometry: tiles of one 124-column strip × R rows (the
-// streaming sweep's strips), one workgroup each, at most one per CU, R ≥ 8
-// where the block allows and ≤ kResMaxRows; the band-coefficient table is
-// sized from the host row classes (the kernel's exact band test).
+static_assert(kResTileRows == dev::kResMaxRows && kResTiles == dev::kResMaxTiles,
+              "the plan's resident geometry (pe/solver_plan.hpp) uses the kernel's limits");
+
+// LDS-resident geometry: the plan's tiling (resident_tiling: tiles of one
+// 124-column strip × R rows — the streaming sweep's strips — one workgroup
+// each, at most one per CU, R ≥ 8 where the block allows and ≤ kResMaxRows);
+// the band-coefficient table is sized from the host row classes (the kernel's
+// exact band test).
 void DeviceSolver::setup_resident() {
   KParams& k = *kp_;
   resident_ = false;
-  const char* e = std::getenv("PE_RESIDENT");
-  if (e && std::atoi(e) == 0) return;
+  const EnvKnobs env = read_env_knobs();
+  if (env.plan.resident && *env.plan.resident == 0) return;
   if (!fused_ || sstep_ || comm_->size() != 1 || blk_.Px * blk_.Py != 1 || overlap_ || k.stamps || opt_.variant != 0)
     return;
-  const int nx = int(blk_.nx);
-  int cus = 256;
-  {
-    int dev = 0;
-    PE_HIP_CHECK(hipGetDevice(&dev));
-    PE_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  }
-  const int nstrips = k.nstrips;
-  if (nstrips > cus) return;
-  const int ntr = std::max(1, std::min(cus / nstrips, nx / 8));
-  if (nx < 2 * ntr) return;
-  std::vector<int> rs(size_t(ntr) + 1);
-  for (int t = 0; t <= ntr; ++t) rs[size_t(t)] = 1 + int(int64_t(t) * nx / ntr);
-  int rcap = 0;
-  for (int t = 0; t < ntr; ++t) rcap = std::max(rcap, rs[size_t(t) + 1] - rs[size_t(t)]);
-  if (rcap > dev::kResMaxRows) return;
+  const int cus = cus_;
+  const std::optional<ResidentTiling> tiling = resident_tiling(blk_.nx, blk_.ny, cus);
+  if (!tiling) return;
+  const int nstrips = tiling->nstrips, ntr = tiling->ntr, rcap = tiling->rcap;
+  const std::vector<int>& rs = tiling->rowstart;
   // band nodes per tile region (rows I0-2 .. I0+R+1, columns J0-2 .. J0+125)
   const int64_t rows_tab = int64_t(rowcls_host_.size() / 4);
   int nb_max = 0;
@@ -283,7 +273,7 @@ void DeviceSolver::setup_resident() {
   r.nbcap = nbcap;
   r.lds_bytes = unsigned(lds);
   r.timeout_ticks = 200000000LL;  // 2 s per barrier wait
-  if (const char* t = std::getenv("PE_RES_TIMEOUT_S")) r.timeout_ticks = (long long)(std::atof(t) * 1e8);
+  if (env.res_timeout_s) r.timeout_ticks = (long long)(*env.res_timeout_s * 1e8);
   PE_HIP_CHECK(hipMalloc(&res_rowstart_, sizeof(int) * rs.size()));
   upload(res_rowstart_, rs.data(), sizeof(int) * rs.size());
   const size_t nedge = size_t(2) * size_t(nwg) * dev::kResEdge, npart = size_t(2) * size_t(nwg) * 8;
@@ -292,7 +282,7 @@ void DeviceSolver::setup_resident() {
   // hardware queue (≈10 ms inside T_solver in a fresh process, profiles/r2_ctor_phases.txt)
   PE_HIP_CHECK(hipMemsetAsync(res_buf_, 0, sizeof(double) * (nedge + npart), stream_));
   PE_HIP_CHECK(hipMalloc(&res_ctr_, sizeof(unsigned) * 8 * 32));
-  if (const char* t = std::getenv("PE_RES_STAMPS"); t && std::atoi(t) == 1) {
+  if (env.res_stamps) {
     nstamps_ = size_t(nwg) * dev::kResStampIters * 8;
     PE_HIP_CHECK(hipMalloc(&stamps_, sizeof(unsigned long long) * nstamps_));
     PE_HIP_CHECK(hipMemsetAsync(stamps_, 0, sizeof(unsigned long long) * nstamps_, stream_));
@@ -304,9 +294,9 @@ void DeviceSolver::setup_resident() {
   r.ctr = res_ctr_;
   r.fault_wg = -1;
   r.fault_late = 0;
-  if (const char* f = std::getenv("PE_FAULT_INJECT"); f && (std::string(f) == "resbarrier" || std::string(f) == "reslate")) {
+  if (env.fault.resbarrier || env.fault.reslate) {
     r.fault_wg = nwg - 1;
-    r.fault_late = std::string(f) == "reslate" ? 1 : 0;
+    r.fault_late = env.fault.reslate ? 1 : 0;
   }
   resident_ = true;
 }

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../hip/kernels.hpp"
+#include "env_knobs.hpp"
 #include "pe/device.hpp"
 
 namespace pe {
@@ -33,7 +34,8 @@ class P2PAllreduceComm final : public DeviceComm {
   explicit P2PAllreduceComm(std::unique_ptr<DeviceComm> base) : base_(std::move(base)) {
     const int P = base_->size(), me = base_->rank();
     if (P > 64) throw std::invalid_argument("p2p allreduce: at most 64 ranks");
-    if (const char* e = std::getenv("PE_P2P_TIMEOUT_S")) timeout_s_ = std::atof(e);
+    const EnvKnobs env = read_env_knobs();
+    if (env.p2p_timeout_s) timeout_s_ = *env.p2p_timeout_s;
     hipStream_t s = nullptr;
     PE_HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
     bool ok = setup(P, me, s);
@@ -56,9 +58,7 @@ class P2PAllreduceComm final : public DeviceComm {
       const double want = 0.5 * double(P) * double(P + 1);
       bool good = h[0] == want && h[1] == -want;
       // PE_FAULT_INJECT=p2ptest@rank:R — rank R's check fails (fallback test)
-      if (const char* e = std::getenv("PE_FAULT_INJECT"); e && std::string(e).rfind("p2ptest@rank:", 0) == 0 &&
-                                                          std::atoi(e + 13) == me)
-        good = false;
+      if (env.fault.p2ptest_rank == me) good = false;
       ok = agree(good, s);
       if (!ok) why_ = good ? "self-test sum wrong on a peer" : "self-test sum wrong on this rank";
     }

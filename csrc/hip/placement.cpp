@@ -18,6 +18,7 @@
 #include <rocprofiler-sdk-roctx/roctx.h>
 
 #include "../hip/kernels.hpp"
+#include "env_knobs.hpp"
 #include "pe/device.hpp"
 #include "solver_internal.hpp"
 
@@ -122,7 +123,7 @@ bool DeviceSolver::placement_search(bool retry) {
   // not adopted.)
   int tries = pts >= 24.0e6 ? 12 : 1;
   if (retry) tries = std::max(1, tries / 2 + 1);  // the kept candidate + half a round
-  if (const char* e = std::getenv("PE_PLACEMENT_TRIES")) tries = std::max(1, std::atoi(e));
+  if (const std::optional<int> e = read_env_knobs().placement_tries) tries = std::max(1, *e);
   const double skip_gb = 8.0;
   // best-class threshold: the single sweep's 40 B/node at ≥ 4.9 TB/s (8192²:
   // ≤ 0.548 ms); the two-step sweep's 48 B/node per sweep at ≥ 4.7 TB/s

@@ -9,6 +9,7 @@
 #include <memory>
 #include <stdexcept>
 #include <array>
+#include <chrono>
 #include <functional>
 #include <map>
 #include <tuple>
@@ -18,6 +19,7 @@
 #include "pe/comm.hpp"
 #include "pe/row_classes.hpp"  // host tables, row classes, the item-layout planner
 #include "pe/solver.hpp"
+#include "pe/solver_plan.hpp"  // the host-only plan of the constructor's decisions
 
 #define PE_HIP_CHECK(expr)                                                                     \
   do {                                                                                         \
@@ -122,6 +124,7 @@ struct DevState;
 struct KParams;
 struct ResParams;
 }  // namespace dev
+struct EnvKnobs;  // the parsed PE_* knobs (csrc/hip/env_knobs.hpp)
 
 class DeviceSolver {
  public:
@@ -275,6 +278,14 @@ class DeviceSolver {
   // overlap: list positions 0 .. n-1 hold the boundary items (0: no overlap)
   int layout_boundary() const { return overlap_ ? lay_.lnb[0] : 0; }
   const LayoutRequest& layout_request() const { return lay_req_; }  // what that list was asked with (occupancy, knobs)
+  // The plan the constructor followed and what it was made with: plan_solver /
+  // finish_plan / plan_chunk of these inputs rebuild it (pe/solver_plan.hpp).
+  const SolverPlan& plan() const { return plan_; }
+  const SolverKnobs& plan_knobs() const { return plan_knobs_; }
+  const DeviceFacts& plan_facts() const { return facts_; }
+  const SolveOptions& options() const { return opt_; }
+  const HaloInputs& halo_inputs() const { return halo_in_; }  // what choose_halo_path asked halo_candidates() with
+  int comm_size() const { return comm_->size(); }
   // First cross-device run diagnostics: hipDeviceCanAccessPeer of this
   // rank's device toward each rank's (1 / 0; -1 the same device; empty on
   // one rank), why the halo push is on / off / fell back, and the transport
@@ -373,6 +384,14 @@ class DeviceSolver {
   void clear_stamps();  // stream-ordered: the next sweep's stamps only
 
  private:
+  // the constructor's steps (device_solver.cpp)
+  void ctor_mark(const char* phase);     // PE_CTOR_TRACE=1: the phase's wall time → stderr
+  void peer_diagnostics();               // collective: peer_access_, shared_dev_
+  void allocate_fields();
+  void allocate_state();
+  void fill_kparams(const EnvKnobs& env);
+  void allocate_stamps();
+  void setup_in_sweep_sums(const EnvKnobs& env);
   void build_tables(int64_t rows_hi, int64_t cols_hi);
   void upload(void* dst, const void* src, size_t bytes);  // set-up data via pinned staging + copy kernel
   void set_plane(double** plane, const double* host, int64_t n);  // set_rhs / set_w0
@@ -448,6 +467,12 @@ class DeviceSolver {
   DeviceComm* comm_;
   std::unique_ptr<DeviceComm> self_;
   SolveOptions opt_;
+  SolverPlan plan_;         // what the constructor set up (pe/solver_plan.hpp)
+  SolverKnobs plan_knobs_;  // the PE_* values it was planned with
+  DeviceFacts facts_;       // the CU count and occupancy it was finished with
+  HaloInputs halo_in_;      // the halo-path choice's inputs (multi-rank single-sweep solvers)
+  bool ctor_trace_ = false;
+  std::chrono::steady_clock::time_point t_mark_;
   hipStream_t stream_ = nullptr;
   bool fused_ = false;
   bool sstep_ = false;    // multi-iteration sweep (fused2.hip / fused3.hip): steps_ iterations per launch
@@ -506,7 +531,6 @@ class DeviceSolver {
   bool ctor_counted_ = false;
   int placement_best_ = 0;
   double placement_job_ms_ = 0;
-  bool tune_ti_ = false;          // rows per item chosen by timing candidate sweeps
   std::vector<float> ti_ms_;      // their per-sweep times
   std::vector<int> ti_rows_;      // the candidates timed
   std::vector<int> ti_alt_;       // the tuning's best two heights (the overlap is timed at both)
@@ -519,7 +543,6 @@ class DeviceSolver {
   bool lay_cache_on_ = false;
   std::function<void()> halo_idle_;        // host work while time_halo_path's sweeps run (the choice's next layouts)
   std::string push_status_ = "off", xr_status_ = "none";
-  int wave_caps_[2] = {0, 0};     // resident waves of the applying / deferring sweep
   int cus_ = 256;                  // compute units of the device (a static layout's first cus_ workgroups run first on their CU)
   bool resident_ = false;
   bool resident_fallback_ = false;  // a resident launch aborted (status 5): switched to the streaming sweep
