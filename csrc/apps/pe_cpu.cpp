@@ -4,7 +4,10 @@
 //          [--threads-sweep 1,4,16] [--norm weighted|unweighted]
 //          [--decomp reference|aspect] [--init zero|random] [--seed S]
 //          [--tol 1e-6] [--max-iter K] [--stage stage0|stage1|stage2|stage3]
-//          [--shift S] [--json] [M N]
+//          [--shift S] [--stop step|residual] [--atol A] [--json] [M N]
+// --stop residual stops on sqrt(g_k) <= max(tol·sqrt(g_0), A), g = h1·h2·(z, r)
+// (pe/problem.hpp Stop); --json then carries "stop", "atol", "res_nat0",
+// "res_nat" and "stop_thr".
 // --shift S (finite, >= 0) solves (A + S·I) w = B, −Δu + S·u = f; the analytic
 // error then reads n/a and --json carries "shift".
 // Replaces: stage0/Withoutopenmp*.cpp main (:176-196), stage1 thread sweep
@@ -28,13 +31,22 @@ static std::vector<int> parse_list(const std::string& s) {
   return v;
 }
 
+// (the stop rule's keys only under --stop residual: the default output stays byte for byte)
+static std::string stop_json(const Problem& P, const SolveResult& r) {
+  if (P.stop != Stop::Residual) return "";
+  char b[256];
+  std::snprintf(b, sizeof(b), ", \"stop\": \"residual\", \"atol\": %.17g, \"res_nat0\": %.17g, \"res_nat\": %.17g, "
+                              "\"stop_thr\": %.17g", P.atol, r.res_nat0, r.res_nat, r.stop_thr);
+  return b;
+}
+
 int main(int argc, char** argv) {
   Args args(argc, argv);
   if (args.flag("help")) {
     std::puts("usage: pe_cpu [--backend serial|omp|ranks] [--ranks P] [--threads T] [--threads-sweep L]\n"
               "              [--norm weighted|unweighted] [--decomp reference|aspect] [--init zero|random]\n"
               "              [--seed S] [--tol D] [--max-iter K] [--stage stage0..3] [--grids 10,20,40] [--shift S]\n"
-              "              [--json] [M N]");
+              "              [--stop step|residual] [--atol A] [--json] [M N]");
     return 0;
   }
   Problem P;
@@ -46,8 +58,13 @@ int main(int argc, char** argv) {
   P.tol = args.getd("tol", 1e-6);
   P.max_iter = args.geti("max-iter", -1);
   P.shift = args.getd("shift", 0.0);
+  const std::string stop = args.get("stop", "step");
+  P.atol = args.getd("atol", 0.0);
   try {
     check_shift(P, "pe_cpu");
+    if (stop != "step" && stop != "residual") throw std::invalid_argument("pe_cpu: --stop must be step or residual");
+    P.stop = stop == "residual" ? Stop::Residual : Stop::Step;
+    check_stop(P, "pe_cpu");
   } catch (const std::invalid_argument& e) {
     std::fprintf(stderr, "%s\n", e.what());
     return 2;
@@ -94,7 +111,7 @@ int main(int argc, char** argv) {
                   "\"max_outside\": %.6e%s}\n",
                   P.M, P.N, r.backend.c_str(), ranks, t, r.Px, r.Py, (long long)r.iters,
                   r.converged ? "true" : "false", r.t.solver, r.t.iterate, r.t.halo, r.t.reduce, r.t.prec,
-                  r.t.dot, r.l2_err, r.max_err, r.max_outside, shift_json);
+                  r.t.dot, r.l2_err, r.max_err, r.max_outside, (std::string(shift_json) + stop_json(P, r)).c_str());
     } else {
       if (sweep.size() > 1) std::printf("Threads = %2d | Time = %.3f s | Iter=%lld\n", t, r.t.solver, (long long)r.iters);
       else std::cout << format_result_legacy(P, r, ranks, stage);

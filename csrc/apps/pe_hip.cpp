@@ -3,7 +3,7 @@
 //
 //   pe_hip [--tol 1e-6] [--max-iter K] [--decomp device|aspect|reference|rows|cols|PxxPy]
 //          [--init zero|random] [--seed S] [--variant 0|1] [--algo auto|classic|fused|two-step|three-step] [--chunk K]
-//          [--graph] [--timing] [--vranks P] [--shift S] [--json] [M N]
+//          [--graph] [--timing] [--vranks P] [--shift S] [--stop step|residual] [--atol A] [--json] [M N]
 //
 // Multi-GPU: `pe_launch -n 8 bin/pe_hip 8192 8192` (or torchrun-style env
 // RANK / WORLD_SIZE / LOCAL_RANK).  The RCCL unique id is exchanged through
@@ -12,6 +12,9 @@
 // --shift S (finite, >= 0) solves (A + S·I) w = B, −Δu + S·u = f, on the
 // classic two-kernel path (--algo auto | classic); the analytic error then
 // reads n/a and --json carries "shift".
+// --stop residual stops on sqrt(g_k) <= max(tol·sqrt(g_0), A), g = h1·h2·(z, r),
+// one iteration per launch (--algo auto | classic | fused); --json then carries
+// "stop", "atol", "res_nat0", "res_nat" and "stop_thr".
 // Output lines follow poisson_mpi_cuda2.cu:1002-1034 (parity) plus the
 // L2/max error against the analytic solution the reference never computes.
 #include <sys/stat.h>
@@ -72,8 +75,13 @@ int main(int argc, char** argv) {
   P.max_iter = args.geti("max-iter", -1);
   P.norm = args.get("norm", "weighted") == "unweighted" ? Norm::Unweighted : Norm::Weighted;
   P.shift = args.getd("shift", 0.0);
+  const std::string stop = args.get("stop", "step");
+  P.atol = args.getd("atol", 0.0);
   try {
     check_shift(P, "pe_hip");
+    if (stop != "step" && stop != "residual") throw std::invalid_argument("pe_hip: --stop must be step or residual");
+    P.stop = stop == "residual" ? Stop::Residual : Stop::Step;
+    check_stop(P, "pe_hip");
   } catch (const std::invalid_argument& e) {
     std::fprintf(stderr, "%s\n", e.what());
     return 2;
@@ -155,7 +163,13 @@ int main(int argc, char** argv) {
     // ("shift" only when non-zero: the unshifted output stays byte for byte)
     char sj[64] = "";
     if (P.shift != 0.0) std::snprintf(sj, sizeof(sj), ", \"shift\": %.17g", P.shift);
-    const std::string shift_json = sj;
+    std::string shift_json = sj;
+    if (P.stop == Stop::Residual) {  // (only under --stop residual: the default output stays byte for byte)
+      char b[256];
+      std::snprintf(b, sizeof(b), ", \"stop\": \"residual\", \"atol\": %.17g, \"res_nat0\": %.17g, \"res_nat\": %.17g, "
+                                  "\"stop_thr\": %.17g", P.atol, r.res_nat0, r.res_nat, r.stop_thr);
+      shift_json += b;
+    }
     if (args.flag("json")) {
       std::printf("{\"M\": %d, \"N\": %d, \"ranks\": %d, \"Px\": %d, \"Py\": %d, \"iters\": %lld, \"converged\": %s, "
                   "\"t_solver\": %.6f, \"t_setup\": %.6f, \"t_construct\": %.6f, \"t_iterate\": %.6f, "

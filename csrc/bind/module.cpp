@@ -57,6 +57,7 @@ py::dict state_dict(const dev::DevState& s) {
   py::dict d;
   d["red_F"] = py::make_tuple(s.red_F[0], s.red_F[1]);
   d["red_G"] = s.red_G[0];
+  d["stop_thr"] = s.red_G[1];  // residual rule: the threshold (0 otherwise)
   d["err"] = py::make_tuple(s.err[0], s.err[1], s.err[2]);
   d["rz_cur"] = s.rz_cur;
   d["alpha"] = s.alpha;
@@ -129,6 +130,7 @@ PYBIND11_MODULE(_native, m) {
 
   py::enum_<Norm>(m, "Norm").value("Weighted", Norm::Weighted).value("Unweighted", Norm::Unweighted);
   py::enum_<Init>(m, "Init").value("Zero", Init::Zero).value("Random", Init::Random);
+  py::enum_<Stop>(m, "Stop").value("Step", Stop::Step).value("Residual", Stop::Residual);
   py::enum_<DecompMode>(m, "DecompMode")
       .value("Reference", DecompMode::Reference)
       .value("Aspect", DecompMode::Aspect)
@@ -152,6 +154,8 @@ PYBIND11_MODULE(_native, m) {
       .def_readwrite("max_iter", &Problem::max_iter)
       .def_readwrite("norm", &Problem::norm)
       .def_readwrite("shift", &Problem::shift)
+      .def_readwrite("stop", &Problem::stop)
+      .def_readwrite("atol", &Problem::atol)
       .def("h1", &Problem::h1)
       .def("h2", &Problem::h2)
       .def("eps", &Problem::eps)
@@ -231,6 +235,9 @@ PYBIND11_MODULE(_native, m) {
       .def_readonly("res_gap", &SolveResult::res_gap)
       .def_readonly("b_norm", &SolveResult::b_norm)
       .def_readonly("restarts", &SolveResult::restarts)
+      .def_readonly("res_nat0", &SolveResult::res_nat0)
+      .def_readonly("res_nat", &SolveResult::res_nat)
+      .def_readonly("stop_thr", &SolveResult::stop_thr)
       .def_property_readonly("grad", [](const SolveResult& r) { return grad_tuple(r.grad); },
                              "(integral, energy, grad_max) where the solve computed them (hip-group on request), else -1s")
       .def_property_readonly("timers", [](const SolveResult& r) { return timers_dict(r.t); });
@@ -697,6 +704,8 @@ PYBIND11_MODULE(_native, m) {
            },
            py::arg("iters"), py::arg("use_graph") = true)
       .def("set_check_tol", &DeviceSolver::set_check_tol, py::arg("on"))
+      .def("set_atol", &DeviceSolver::set_atol, py::arg("atol"),
+           "the residual rule's absolute floor of the next solves (ValueError under the step-size rule, or not finite / < 0)")
       .def("set_init", &DeviceSolver::set_init, py::arg("init"), py::arg("seed") = 1234, py::arg("amp") = 0.05)
       .def(
           "set_rhs",

@@ -16,6 +16,15 @@ void check_shift(const Problem& P, const char* who) {
                                 "): a negative shift makes the system indefinite");
 }
 
+void check_stop(const Problem& P, const char* who) {
+  if (P.stop != Stop::Step && P.stop != Stop::Residual)
+    throw std::invalid_argument(std::string(who) + ": stop must be \"step\" or \"residual\"");
+  if (!std::isfinite(P.atol) || P.atol < 0.0)
+    throw std::invalid_argument(std::string(who) + ": atol must be finite and >= 0 (got " + std::to_string(P.atol) + ")");
+  if (P.atol != 0.0 && P.stop != Stop::Residual)
+    throw std::invalid_argument(std::string(who) + ": atol belongs to the stop rule \"residual\"; the step-size rule has none");
+}
+
 std::vector<double> block_field(const double* g, int M, int N, const Block& blk, int ring) {
   if (!g) throw std::invalid_argument("block_field: null array");
   if (ring != 0 && ring != 1) throw std::invalid_argument("block_field: ring must be 0 or 1");

@@ -44,6 +44,7 @@ SolverPlan plan_solver(const Problem& prob, const Block& blk, int comm_size, con
   // on every decomposition: the single-sweep, multi-step and resident kernels
   // do not carry the shift, and nothing below may launch one of them.
   check_shift(prob, "DeviceSolver");
+  check_stop(prob, "DeviceSolver");
   const bool shifted = prob.shift != 0.0;
   if (shifted && opt.algo >= 2)
     throw std::invalid_argument(
@@ -83,6 +84,14 @@ SolverPlan plan_solver(const Problem& prob, const Block& blk, int comm_size, con
     if (opt.algo == 4 && !three_ok)
       throw std::invalid_argument(
           "three-step sweep: single-rank blocks of >= 8 x 8 nodes, row slabs of >= 12 rows or 2-D blocks of >= 12 x 12");
+    // The residual stop rule (Problem::stop) tests an iterate at the top of the
+    // next iteration: the one-iteration kernels do (kF, kS / kRed, kResident);
+    // the multi-step sweeps do not carry it.  After every other refusal.
+    const bool res_rule = prob.stop == Stop::Residual;
+    if (res_rule && opt.algo >= 3)
+      throw std::invalid_argument(
+          "algo two-step / three-step: the multi-step sweeps implement the step-size stop rule only; a problem with "
+          "stop = \"residual\" runs algo auto, classic or fused");
     // auto: every single-rank block the LDS-resident kernel cannot hold
     // (1x MI355X, fresh processes, T_solver two-step vs single sweep:
     // 1600×2400 0.110 vs 0.127 s, 2048² 0.113 vs 0.133, 4096² 0.378 vs 0.584,
@@ -96,6 +105,7 @@ SolverPlan plan_solver(const Problem& prob, const Block& blk, int comm_size, con
     bool auto_ms = slabs(8) || grid2d(12) || vgroup(12) || !pl.resident_likely;
     int want = 3;
     if (knobs.steps) want = std::max(1, std::min(3, *knobs.steps));
+    if (res_rule) want = 1;  // one iteration per launch on every decomposition (PE_STEPS is ignored)
     pl.steps = 1;
     if (opt.algo == 3) pl.steps = 2;
     else if (opt.algo == 4) pl.steps = 3;

@@ -181,6 +181,7 @@ class HaloExchanger {
 SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const SolveOptions& opt,
                     std::vector<double>* w_out, const UserFields& uf) {
   check_shift(P, "cpu_pcg");
+  check_stop(P, "cpu_pcg");
   const auto t_start = clk::now();
   SolveResult res;
   res.backend = opt.threads > 1 ? "cpu-omp" : "cpu-serial";
@@ -233,11 +234,24 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
   const double* r = f.r.data();
   double zr_old = row_sum(blk, T, [&](int64_t c) { return z[c] * r[c]; }) * h1 * h2;
   comm.allreduce_sum(&zr_old, 1);
+  // Residual rule: iterate k is tested at the top of iteration k + 1 against a
+  // threshold fixed from g_0 (the reduced sum: every rank decides alike).
+  const bool res_rule = P.stop == Stop::Residual;
+  const double thr = res_rule ? stop_threshold(P, zr_old) : -1.0;
+  if (res_rule) {
+    res.res_nat0 = std::sqrt(zr_old);
+    res.stop_thr = thr;
+  }
   res.t.setup = secs(t_start, clk::now());
 
   const auto t_loop = clk::now();
   int64_t iter = 0;
   for (int64_t k = 1; k <= max_iter; ++k) {
+    if (res_rule && std::sqrt(zr_old) <= thr) {  // (a non-finite g is never met: today's tests below)
+      res.converged = true;
+      res.res_nat = std::sqrt(zr_old);
+      break;
+    }
     iter = k;
     auto t0 = clk::now();
     halo.run(f.p.data(), comm);
@@ -259,7 +273,7 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
       res.nonfinite = true;
       break;
     }
-    if (std::fabs(den) < 1e-15) {
+    if (cg_breakdown(den, zr_old, res_rule)) {
       res.breakdown = true;
       break;
     }
@@ -311,7 +325,7 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
     if (opt.keep_history) res.history.push_back(gdiff);
     if (opt.log_every > 0 && comm.rank() == 0 && (k % opt.log_every) == 0)
       std::fprintf(stderr, "[pe] iter %lld  |dw| = %.6e  (z,r) = %.6e\n", (long long)k, gdiff, zr_new);
-    if (gdiff < P.tol) {
+    if (!res_rule && gdiff < P.tol) {
       res.converged = true;
       zr_old = zr_new;
       break;
@@ -375,6 +389,7 @@ SolveResult cpu_pcg_threads(const Problem& P, int ranks, DecompMode mode, const 
 SolveResult cpu_pcg_threads(const Problem& P, const ProcessGrid& pg, const SolveOptions& opt,
                             std::vector<double>* w_out, const UserFields& uf) {
   check_shift(P, "cpu_pcg");  // (before any rank thread starts)
+  check_stop(P, "cpu_pcg");
   const int ranks = pg.Px * pg.Py;
   auto group = make_thread_group(ranks);
   std::vector<SolveResult> results(ranks);

@@ -373,6 +373,7 @@ void DeviceSolver::fill_kparams(const EnvKnobs& env) {
   k.D_out = (k.inv_eps + k.inv_eps) / k.h1sq + (k.inv_eps + k.inv_eps) / k.h2sq;
   k.dinv_in = 1.0 / ((1.0 + 1.0) * k.ih1sq + (1.0 + 1.0) * k.ih2sq);
   k.dinv_out = 1.0 / ((k.inv_eps + k.inv_eps) * k.ih1sq + (k.inv_eps + k.inv_eps) * k.ih2sq);
+  k.stop_res = prob_.stop == Stop::Residual ? 1 : 0;
   k.shift = prob_.shift;
   if (k.shift != 0.0) {  // the diagonal of A + σI in the two uniform classes (pe/fields.hpp; the band adds σ in cset)
     k.D_in = shifted_diag(k.D_in, k.shift);
@@ -448,6 +449,23 @@ void DeviceSolver::set_check_tol(bool on) {
   kp_->check_tol = on ? 1 : 0;
   for (auto& g : graphs_) PE_HIP_CHECK(hipGraphExecDestroy(g.second));  // captured with the old parameters
   graphs_.clear();
+}
+
+void DeviceSolver::set_atol(double atol) {
+  Problem p = prob_;
+  p.atol = atol;
+  check_stop(p, "DeviceSolver");
+  prob_.atol = atol;  // (host only: the next solve's threshold; no kernel parameter, cached graphs stay)
+}
+
+double DeviceSolver::stop_g0(const DevState& s) const {
+  // the expressions the kernels test with: kF's (red_G · h1) · h2, sweep_scalars' fs · (h1 · h2)
+  return fused_ ? s.fs[1][0] * (prob_.h1() * prob_.h2()) : (s.red_G[0] * prob_.h1()) * prob_.h2();
+}
+
+void DeviceSolver::enqueue_stop_threshold(double thr, double nat0) {
+  dev::launch_set_stop(*kp_, thr, nat0, stream_);
+  PE_HIP_CHECK(hipGetLastError());
 }
 
 void DeviceSolver::set_init(Init init, uint64_t seed, double amp) {
@@ -1301,6 +1319,18 @@ SolveResult DeviceSolver::solve() {
     reset();
   }
   PE_HIP_CHECK(hipStreamSynchronize(stream_));
+  // Residual rule: the threshold from the reduced g_0 (the same bits on every
+  // rank) into the device state, on the solver stream, before the first
+  // iteration is enqueued; a resumed solve keeps the one its file carries.
+  const bool res_rule = prob_.stop == Stop::Residual;
+  auto set_threshold = [&]() {
+    if (!res_rule || !opt_.resume_path.empty()) return;
+    DevState s0;
+    read_state(&s0);
+    const double g0 = stop_g0(s0);
+    enqueue_stop_threshold(stop_threshold(prob_, g0), std::sqrt(g0));
+  };
+  set_threshold();
   res.t.construct = construct;
   res.t.setup = construct + secs(t_start, clk::now());
   const int64_t ck_every = opt_.checkpoint_path.empty() ? 0 : opt_.checkpoint_every;
@@ -1390,6 +1420,7 @@ SolveResult DeviceSolver::solve() {
           samples_.clear();
           if (!opt_.resume_path.empty()) load_checkpoint(opt_.resume_path + ".r" + std::to_string(blk_.rank));
           else reset();
+          set_threshold();  // (the reset zeroed the state)
           enq = start_iter;
           sample_iter_ = start_iter;
           stop = false;
@@ -1500,6 +1531,11 @@ SolveResult DeviceSolver::solve() {
     PE_HIP_CHECK(hipStreamSynchronize(stream_));
   }
   res.zr = hs.rz_cur;
+  if (res_rule) {  // (the terminal paths of the rule leave g_K in rz_cur)
+    res.res_nat0 = hs.err[3];
+    res.stop_thr = hs.red_G[1];
+    if (res.converged) res.res_nat = std::sqrt(hs.rz_cur);
+  }
   if (opt_.compute_error) {
     // (a user right-hand side, or a shifted operator, without a user exact solution has nothing to compare with: -1)
     const bool no_exact = (rhs_dev_ || prob_.shift != 0.0) && !exact_dev_;
@@ -1711,6 +1747,13 @@ SolveResult device_solve_group(const Problem& P, const ProcessGrid& pg, const So
     reduce(dp + ranks, 1, 0);
   }
   PE_HIP_CHECK(hipStreamSynchronize(s0));
+  const bool res_rule = P.stop == Stop::Residual;
+  if (res_rule) {  // the threshold from the reduced g_0 into every block's state, each on its own stream
+    DevState st0;
+    s[0]->read_state(&st0);
+    const double g0 = s[0]->stop_g0(st0);
+    for (int r = 0; r < ranks; ++r) s[r]->enqueue_stop_threshold(stop_threshold(P, g0), std::sqrt(g0));
+  }
   SolveResult res;
   res.t.setup = secs(t_start, clk::now());
   const auto t_loop = clk::now();
@@ -1818,6 +1861,11 @@ SolveResult device_solve_group(const Problem& P, const ProcessGrid& pg, const So
   if (hs.status == 5) throw std::runtime_error("single-sweep: boundary partials never arrived (internal error)");
   res.last_diff = hs.last_diff;
   res.zr = hs.rz_cur;
+  if (res_rule) {
+    res.res_nat0 = hs.err[3];
+    res.stop_thr = hs.red_G[1];
+    if (res.converged) res.res_nat = std::sqrt(hs.rz_cur);
+  }
   if (opt.compute_error) {
     const bool no_exact = (uf.rhs || df.rhs || P.shift != 0.0) && !(uf.exact || df.exact);
     res.l2_err = no_exact ? -1.0 : std::sqrt(hs.err[0] * P.h1() * P.h2());

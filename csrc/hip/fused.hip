@@ -156,13 +156,19 @@ struct Scal {
   bool first;
   long long kiter;
   double g, alpha, beta, diff, zc, den;
+  double thr;  // residual rule (k.stop_res): the threshold, st->red_G[1]
 };
+// RS (here and below): the residual stop rule, KParams::stop_res — a template
+// flag, so the step-size rule's instantiations are the code they were before it.
+template <bool RS = false>
 __device__ __forceinline__ Scal sweep_scalars(const KParams& k, const DevState* st, int par) {
   Scal c;
   c.first = st->started == 0;
   c.kiter = st->iter + 1;
   c.g = c.alpha = c.beta = c.diff = c.zc = 0.0;
   c.den = 1.0;
+  c.thr = 0.0;
+  if constexpr (RS) c.thr = st->red_G[1];
   if (!c.first) {
     const double hh = k.h1 * k.h2;
     const double* R = st->fs[par ^ 1];
@@ -182,19 +188,30 @@ __device__ __forceinline__ Scal sweep_scalars(const KParams& k, const DevState* 
 // last: a deferring sweep (WM = 0) that converged or hit the cap — it only
 // adds its own α_k p_k to w.  A pure function of the scalars, so every block
 // of the sweep and of its reduction kernel decides the same.
+// rstop (residual rule, k.stop_res): the iterate this sweep starts from, k =
+// kiter − 1, already meets sqrt(g_k) ≤ thr — the solve ends converged with
+// iter = k, before this sweep's work, on the breakdown path's route (a pending
+// α_{k−1} p_{k−1} is applied); tested before the breakdown tests, and never
+// true for a non-finite g.  The step-size test is not made under that rule.
 struct Term {
-  bool brk, bad, last, conv;
+  bool brk, bad, last, conv, rstop;
 };
-template <int WM>
+template <int WM, bool RS = false>
 __device__ __forceinline__ Term sweep_term(const KParams& k, const Scal& c) {
-  Term t{false, false, false, false};
+  Term t{false, false, false, false, false};
   if (c.first) return t;
+  if constexpr (RS) {
+    if (k.check_tol && sqrt(c.g) <= c.thr) {
+      t.rstop = t.brk = true;
+      return t;
+    }
+  }
   // breakdown first (reference :413 tests |den| before α exists); a
   // non-finite ‖Δw‖ only matters when α was formed
-  const bool tiny = fabs(c.den) < 1e-15;
+  const bool tiny = cg_breakdown(c.den, c.g, RS);
   t.bad = !isfinite(c.den) || !isfinite(c.g) || (!tiny && !isfinite(c.diff));
   t.brk = t.bad || tiny;
-  t.conv = k.check_tol && c.diff < k.tol;
+  t.conv = !RS && k.check_tol && c.diff < k.tol;
   t.last = !t.brk && WM == 0 && (t.conv || c.kiter >= k.max_iter);
   return t;
 }
@@ -203,7 +220,10 @@ __device__ __forceinline__ Term sweep_term(const KParams& k, const Scal& c) {
 // while another block of the grid may still be reading the state it read at
 // entry: the ticket orders every block's reads before this write).
 __device__ __forceinline__ void sweep_terminal(const KParams& k, DevState* st, const Scal& c, const Term& t) {
-  if (t.brk) {
+  if (t.rstop) {  // (st->iter stays kiter − 1: the iterate tested)
+    st->rz_cur = c.g;
+    st->status = 1;
+  } else if (t.brk) {
     st->status = t.bad ? 4 : 2;
     st->iter = c.kiter;
   } else {
@@ -221,7 +241,7 @@ __device__ __forceinline__ void sweep_terminal(const KParams& k, DevState* st, c
 }
 
 // State update after a sweep's sums t[7] are known (one thread).
-template <int WM>
+template <int WM, bool RS = false>
 __device__ __forceinline__ void sweep_finalize(const KParams& k, DevState* st, int par, const Scal& c,
                                                const double (&t)[7]) {
 #pragma unroll
@@ -241,7 +261,7 @@ __device__ __forceinline__ void sweep_finalize(const KParams& k, DevState* st, i
     st->last_diff = c.diff;
     if (k.hist && c.kiter <= k.hist_n) k.hist[c.kiter - 1] = c.diff;
     st->iter = c.kiter;
-    if (k.check_tol && c.diff < k.tol) {
+    if (!RS && k.check_tol && c.diff < k.tol) {
       st->status = 1;
       st->done = 1;
     } else if (c.kiter >= k.max_iter) {
@@ -264,7 +284,7 @@ __device__ __forceinline__ void slow_inject(const KParams& k) {
   }
 }
 
-template <int WM>
+template <int WM, bool RS = false>
 __device__ __forceinline__ void finalize_block(const KParams& k, DevState* st, int par, const Scal& sc,
                                                double (&t)[7]) {
   __shared__ double v[8];
@@ -280,7 +300,7 @@ __device__ __forceinline__ void finalize_block(const KParams& k, DevState* st, i
 #pragma unroll
       for (int n = 0; n < 7; ++n) t[n] = v[n];
   }
-  if (threadIdx.x == 0) sweep_finalize<WM>(k, st, par, sc, t);
+  if (threadIdx.x == 0) sweep_finalize<WM, RS>(k, st, par, sc, t);
 }
 
 __device__ __forceinline__ void wave_sum7(double (&v)[7]) {
@@ -316,7 +336,7 @@ __device__ __forceinline__ unsigned long long rtc() {
 // also stored into the x-neighbours' fine-grained receive buffers over xGMI
 // (system-scope write-through stores, drained and released before the item
 // ends, so they are delivered before this rank's cross-rank-sum flags).
-template <int OCC, int PF, bool NT, int WM, bool STAMP = false, bool PUSH = false>
+template <int OCC, int PF, bool NT, int WM, bool STAMP = false, bool PUSH = false, bool RS = false>
 __global__ __launch_bounds__(TJ) __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OCC : 1))) void kS(KParams k, int par) {
   DevState* st = k.st;
   const unsigned long long t_entry = STAMP ? rtc() : 0ull;
@@ -328,7 +348,7 @@ __global__ __launch_bounds__(TJ) __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OC
   const int done = st->done, wpend = st->wpend;
   const double alpha_st = st->alpha;
   // ---- scalars of this sweep from the previous sweep's global sums ----
-  const Scal sc = sweep_scalars(k, st, par);
+  const Scal sc = sweep_scalars<RS>(k, st, par);
   __shared__ double sm[32];
   __shared__ int sflag;
   __shared__ WaveTV tvs[kWPB];
@@ -450,7 +470,7 @@ __global__ __launch_bounds__(TJ) __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OC
   auto leave = [&]() -> bool {
     state_ok = true;
     if (done) return true;
-    const Term tm = sweep_term<WM>(k, sc);
+    const Term tm = sweep_term<WM, RS>(k, sc);
     if (tm.brk || tm.last) {
       // breakdown: apply only the pending term; last sweep of the solve: only
       // w changes (w += α_k p_k, pointwise).  The state is written by the
@@ -857,22 +877,22 @@ __global__ __launch_bounds__(TJ) __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OC
   if (publish_last_nm<7>(k.partial, v, &st->ticket[0], &sflag, sm)) {  // (kcommon.hpp: n-major partials)
     double t[7];
     reduce_partials_nm<7>(k.partial, t, sm);
-    finalize_block<WM>(k, st, par, sc, t);
+    finalize_block<WM, RS>(k, st, par, sc, t);
     if (threadIdx.x == 0) __hip_atomic_store(&st->ticket[0], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
 // Dynamic-queue sweeps: deterministic reduction of the per-item sums (item
 // order, fixed per-block ranges) and the state update.
-template <int WM>
+template <int WM, bool RS = false>
 __global__ __launch_bounds__(TJ) void kRed(KParams k, int par) {
   DevState* st = k.st;
   if (st->done) return;  // includes a breakdown / last sweep handled by kS
   __shared__ double sm[32];
   __shared__ int sflag;
-  const Scal sc = sweep_scalars(k, st, par);
+  const Scal sc = sweep_scalars<RS>(k, st, par);
   {
-    const Term tm = sweep_term<WM>(k, sc);
+    const Term tm = sweep_term<WM, RS>(k, sc);
     if (tm.brk || tm.last) {  // the sweep stopped early (kS): only the terminal state is left to write
       if (arrive_last(&st->ticket[1], gridDim.x, &sflag) && threadIdx.x == 0) {
         sweep_terminal(k, st, sc, tm);
@@ -915,7 +935,7 @@ __global__ __launch_bounds__(TJ) void kRed(KParams k, int par) {
   if (publish_last_nm<7>(k.partial, v, &st->ticket[1], &sflag, sm)) {  // (kcommon.hpp: n-major partials)
     double t[7];
     reduce_partials_nm<7>(k.partial, t, sm);
-    finalize_block<WM>(k, st, par, sc, t);
+    finalize_block<WM, RS>(k, st, par, sc, t);
     if (threadIdx.x == 0) __hip_atomic_store(&st->ticket[1], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
@@ -925,14 +945,14 @@ __global__ __launch_bounds__(TJ) void kRed(KParams k, int par) {
 // its ≈10 µs in that fan-in.  Thread t sums items t, t+1024, … (8 loads in
 // flight), then a fixed wave → workgroup tree: deterministic.
 constexpr int kRed1Threads = 1024;
-template <int WM>
+template <int WM, bool RS = false>
 __global__ __launch_bounds__(kRed1Threads) void kRed1(KParams k, int par) {
   DevState* st = k.st;
   const int done = st->done;
-  const Scal sc = sweep_scalars(k, st, par);
+  const Scal sc = sweep_scalars<RS>(k, st, par);
   if (done) return;
   {
-    const Term tm = sweep_term<WM>(k, sc);
+    const Term tm = sweep_term<WM, RS>(k, sc);
     if (tm.brk || tm.last) {  // the sweep stopped early (kS): only the terminal state is left to write
       if (threadIdx.x == 0) sweep_terminal(k, st, sc, tm);
       return;
@@ -983,7 +1003,7 @@ __global__ __launch_bounds__(kRed1Threads) void kRed1(KParams k, int par) {
       for (int w = 0; w < kRed1Threads / 64; ++w) t[q] += sm[q][w];
     }
   }
-  finalize_block<WM>(k, st, par, sc, t);
+  finalize_block<WM, RS>(k, st, par, sc, t);
 }
 
 // Apply a pending α_k p_k (p_k = p-plane of x[wpar]) before w is read.
@@ -1175,6 +1195,11 @@ void launch_coef_fast(const KParams& k, double* a, double* b, double* dinv, hipS
 // and the plain march's unroll is tied to it).
 template <int WM, class F>
 static auto with_kS(const KParams& k, F&& f) {
+  if (k.stop_res) {  // the residual stop rule's instantiations
+    if (k.stamps) return f(kS<2, 4, true, WM, true, false, true>);
+    if (k.push) return f(kS<2, 4, true, WM, false, true, true>);
+    return f(kS<2, 4, true, WM, false, false, true>);
+  }
   if (k.stamps) return f(kS<2, 4, true, WM, true>);
   if (k.push) return f(kS<2, 4, true, WM, false, true>);
   return f(kS<2, 4, true, WM>);
@@ -1208,6 +1233,11 @@ void launch_red(const KParams& k, int par, hipStream_t s) {
   // vs 10 µs for 64 blocks, tools/jobs/red_trace.sh): only tiny lists
   constexpr int red1_max = 4000;
   if (k.nslots <= red1_max) {
+    if (k.stop_res) {
+      if (par == 0) hipLaunchKernelGGL((kRed1<0, true>), dim3(1), dim3(kRed1Threads), 0, s, k, par);
+      else hipLaunchKernelGGL((kRed1<2, true>), dim3(1), dim3(kRed1Threads), 0, s, k, par);
+      return;
+    }
     if (par == 0) hipLaunchKernelGGL(kRed1<0>, dim3(1), dim3(kRed1Threads), 0, s, k, par);
     else hipLaunchKernelGGL(kRed1<2>, dim3(1), dim3(kRed1Threads), 0, s, k, par);
     return;
@@ -1216,6 +1246,11 @@ void launch_red(const KParams& k, int par, hipStream_t s) {
     // 8192² (44 k slots, 2.8 MB): 4 / 16 / 64 / 128 / 512 blocks = 26.7 / 13.5 /
     // 10.1 / 10.8 / 11.6 µs — load parallelism first, then the ticket fan-in
     const int rb = std::max(1, std::min(64, (k.nslots + 255) / 256));
+    if (k.stop_res) {
+      if (par == 0) hipLaunchKernelGGL((kRed<0, true>), dim3(unsigned(rb)), dim3(TJ), 0, s, k, par);
+      else hipLaunchKernelGGL((kRed<2, true>), dim3(unsigned(rb)), dim3(TJ), 0, s, k, par);
+      return;
+    }
     if (par == 0) hipLaunchKernelGGL(kRed<0>, dim3(unsigned(rb)), dim3(TJ), 0, s, k, par);
     else hipLaunchKernelGGL(kRed<2>, dim3(unsigned(rb)), dim3(TJ), 0, s, k, par);
   }

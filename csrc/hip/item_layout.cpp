@@ -259,7 +259,7 @@ void DeviceSolver::setup_resident() {
   const int nbcap = nb_max + 8;
   const size_t lds = dev::resident_lds_bytes(rcap, nbcap);
   if (lds > 163840) return;
-  const int per_cu = dev::resident_max_blocks_per_cu(lds);
+  const int per_cu = dev::resident_max_blocks_per_cu(lds, k.stop_res != 0);
   const int nwg = ntr * nstrips;
   if (per_cu < 1 || nwg > per_cu * cus) return;
   if (nwg > dev::kResMaxTiles) return;  // the kernel's sum gather covers 256 tiles (parts with > 256 CUs)

@@ -60,6 +60,18 @@ __global__ __launch_bounds__(TJ) void kF(KParams k, int par) {
   __shared__ int sflag;
 
   const double rz_new = (st->red_G[0] * k.h1) * k.h2;
+  // Residual rule: iterate k = st->iter is tested here, at the top of
+  // iteration k + 1, on the reduced (z, r) every block reads alike (NaN ≤ thr
+  // is false: a non-finite g goes on to kG's tests).  One thread writes the
+  // terminal state, as kG's breakdown path does; st->iter stays k.
+  if (k.stop_res && k.check_tol && sqrt(rz_new) <= st->red_G[1]) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      st->rz_cur = rz_new;
+      st->status = 1;
+      st->done = 1;
+    }
+    return;
+  }
   const double beta = rz_new / st->rz_cur;
   const double* __restrict__ pold = k.p[par ^ 1];
   double* __restrict__ pnew = k.p[par];
@@ -244,7 +256,7 @@ __global__ __launch_bounds__(TJ) void kG(KParams k, int par) {
   const double den = (st->red_F[0] * k.h1) * k.h2;
   const long long kiter = st->iter + 1;
   const bool bad = !isfinite(den) || !isfinite(st->rz_cur);
-  if (bad || fabs(den) < 1e-15) {  // breakdown / non-finite: stop before touching w (reference :413)
+  if (bad || cg_breakdown(den, st->rz_cur, k.stop_res != 0)) {  // breakdown / non-finite: stop before touching w (reference :413)
     if (blockIdx.x == 0 && threadIdx.x == 0) {
       st->status = bad ? 4 : 2;
       st->iter = kiter;
@@ -375,7 +387,7 @@ __global__ __launch_bounds__(TJ) void kG(KParams k, int par) {
       st->last_diff = diff;
       if (k.hist && kiter <= k.hist_n) k.hist[kiter - 1] = diff;
       st->iter = kiter;
-      if (k.check_tol && diff < k.tol) {
+      if (k.check_tol && !k.stop_res && diff < k.tol) {
         st->status = 1;
         st->done = 1;
       } else if (kiter >= k.max_iter) {
@@ -933,6 +945,10 @@ __global__ void kRestart3(KParams k) {
 // PE_FAULT_INJECT=drift@iter:K (test hook): w(li, lj) += v behind the
 // recurrence's back — its r no longer is B − A w, which the end-of-solve
 // residual check must see (and the three-step solve restart from).
+__global__ void kSetStop(DevState* st, double thr, double nat0) {
+  st->red_G[1] = thr;
+  st->err[3] = nat0;
+}
 __global__ void kPokeW(KParams k, int64_t li, int64_t lj, double v) { k.w[li * k.wpitch + lj] += v; }
 
 __global__ void kGroupReduce(double* const* bufs, int nranks, int n, int is_max) {
@@ -1179,6 +1195,9 @@ void launch_zero_p(const KParams& k, int b, hipStream_t s) {
   hipLaunchKernelGGL(kZeroP, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, b);
 }
 void launch_restart3(const KParams& k, hipStream_t s) { hipLaunchKernelGGL(kRestart3, dim3(1), dim3(1), 0, s, k); }
+void launch_set_stop(const KParams& k, double thr, double nat0, hipStream_t s) {
+  hipLaunchKernelGGL(kSetStop, dim3(1), dim3(1), 0, s, k.st, thr, nat0);
+}
 void launch_poke_w(const KParams& k, int64_t li, int64_t lj, double v, hipStream_t s) {
   hipLaunchKernelGGL(kPokeW, dim3(1), dim3(1), 0, s, k, li, lj, v);
 }

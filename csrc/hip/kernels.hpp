@@ -30,8 +30,9 @@ namespace dev {
 // Device-resident solver state (one per rank).
 struct DevState {
   double red_F[2];   // Œ£(Ap¬∑p), Œ£(p¬∑p) ‚Äî local, then global after allreduce
-  double red_G[2];   // Œ£(z¬∑r) ‚Äî local, then global; [1] pad
-  double err[4];     // Œ£(w-u)¬≤ in D, max|w-u| in D, max|w| outside D, pad
+  double red_G[2];   // Œ£(z¬∑r) ‚Äî local, then global; [1]: the residual rule's threshold (KParams::stop_res;
+                     // written by the host after the initial reduction, never reduced: the sums take [0] only)
+  double err[4];     // Œ£(w-u)¬≤ in D, max|w-u| in D, max|w| outside D, [3]: the residual rule's sqrt(g_0)
   double rz_cur;     // (z, r) of the previous iteration, h-weighted
   double alpha, beta, last_diff;
   long long iter;    // completed iterations
@@ -250,8 +251,13 @@ struct KParams {
   // Problem::shift œÉ of A + œÉI (classic layout and the operator pass only: the
   // launch wrappers of kernels.hip pick their SHIFT instantiations when it is
   // non-zero; D_in / D_out / dinv_in / dinv_out then hold the shifted diagonal).
-  // Last member: every other kernarg offset stays where it was.
   double shift;
+  // Problem::stop == Residual: the iterate is tested at the top of the next
+  // iteration, sqrt(g) ‚â§ st->red_G[1], instead of the step size after it (kF,
+  // kS / kRed through sweep_term, kResident; the multi-step sweeps never run
+  // under it).  0: the step-size rule, today's code.
+  // Last member: every other kernarg offset stays where it was.
+  int stop_res;
 };
 // KParams::mlimit of the three-step replay launch (DevState::fixj)
 constexpr int kReplay3 = -2;
@@ -297,7 +303,8 @@ constexpr int kResMaxTiles = 256;  // the per-iteration sum gather reads ‚â§ 4 √
 size_t resident_lds_bytes(int rcap, int nbcap);
 // Launch n iterations (the caller zeroes rp.ctr on the same stream first).
 void launch_resident(const KParams& k, const ResParams& rp, hipStream_t s);
-int resident_max_blocks_per_cu(size_t lds_bytes);
+// (stop_res: the instantiation of the residual stop rule, KParams::stop_res)
+int resident_max_blocks_per_cu(size_t lds_bytes, bool stop_res = false);
 
 void launch_init(const KParams& k, int init_random, unsigned long long seed, double amp, int variant,
                  hipStream_t s);
@@ -354,6 +361,8 @@ void launch_unpack_r(const KParams& k, hipStream_t s);
 void launch_w_to_p(const KParams& k, int b, hipStream_t s);   // owned w ‚Üí the p-plane of x[b]
 void launch_zero_p(const KParams& k, int b, hipStream_t s);   // the p-plane of x[b] ‚Üê 0 (halos included)
 void launch_restart3(const KParams& k, hipStream_t s);        // three-step restart state (kRestart3)
+// Residual rule: st->red_G[1] ‚Üê thr, st->err[3] ‚Üê nat0 (one thread, stream-ordered).
+void launch_set_stop(const KParams& k, double thr, double nat0, hipStream_t s);
 void launch_poke_w(const KParams& k, int64_t li, int64_t lj, double v, hipStream_t s);  // fault hook
 // 4-byte-word copy by a kernel (bytes % 4 == 0); either side may be pinned
 // host memory (to_host: system-scope fence after the stores).

@@ -94,6 +94,9 @@ struct Coef {
 
 // (wave_sum63: kcommon.hpp)
 
+// RSTOP: the residual stop rule (KParams::stop_res) — an instantiation of its
+// own, so the step-size rule's kernel is the code it was before the rule.
+template <bool RSTOP>
 __global__ __launch_bounds__(RT, 1) void kResident(KParams k, ResParams rp) {
   extern __shared__ double lds_raw[];
   DevState* st = k.st;
@@ -231,6 +234,32 @@ __global__ __launch_bounds__(RT, 1) void kResident(KParams k, ResParams rp) {
     stp = (rp.stamps && it < kResStampIters) ? rp.stamps + (size_t(wg) * kResStampIters + it) * 8 : nullptr;
     stamp(0);
     const long long kiter = iter + 1;
+    // ---- residual rule (fused.hip sweep_term's rstop): iterate `iter` is
+    // tested before anything of iteration kiter is formed.  Every workgroup
+    // holds the same S (gathered in one order from the same partials), so all
+    // decide alike, here, before this iteration's first barrier; w in registers
+    // already holds every term up to iterate `iter`.  alpha / beta / diff / g
+    // still hold iteration `iter`'s values when it ran in this launch.  The
+    // threshold is read here, under the rule only (no kernel ever writes that
+    // slot), so the step-size rule's loop carries nothing for it.
+    if (RSTOP && k.check_tol && sqrt(S[0] * hh) <= st->red_G[1]) {
+      if (wg == 0 && tid == 0) {
+        if (it == 0) entered_all();
+        if (it > 0) {
+          st->gprev = g;
+          st->alpha = alpha;
+          st->beta = beta;
+          st->last_diff = diff;
+        }
+        st->rz_cur = S[0] * hh;
+        st->iter = iter;
+        st->status = 1;
+        st->done = 1;
+        st->wpend = 0;
+      }
+      stopped = true;
+      break;
+    }
     // ---- scalars (fused.hip sweep_scalars / sweep_term, iterations only) ----
     g = S[0] * hh;
     beta = iter == 0 ? 0.0 : g / gprev;
@@ -238,10 +267,10 @@ __global__ __launch_bounds__(RT, 1) void kResident(KParams k, ResParams rp) {
     alpha = g / den;
     const double pn2 = fmax(S[4] + 2.0 * beta * S[5] + beta * beta * S[6], 0.0);
     diff = k.weighted ? fabs(alpha) * sqrt(pn2 * hh) : fabs(alpha) * sqrt(pn2);
-    const bool tiny = fabs(den) < 1e-15;  // breakdown before α (reference :413)
+    const bool tiny = cg_breakdown(den, g, RSTOP);  // breakdown before α (reference :413)
     const bool bad = !isfinite(den) || !isfinite(g) || (!tiny && !isfinite(diff));
     const bool brk = bad || tiny;
-    const bool conv = k.check_tol && diff < k.tol;
+    const bool conv = !RSTOP && k.check_tol && diff < k.tol;
     const bool last = !brk && (conv || kiter >= k.max_iter);
     if (brk) {  // reference :413 — stop before this iteration's update
       if (wg == 0 && tid == 0) {
@@ -572,14 +601,15 @@ size_t resident_lds_bytes(int rcap, int nbcap) {
   return rc4 * 64 * 16 * 3 + rc4 * 64 * 4 + size_t(nbcap) * 4 * 8 + size_t(RW * 8 + 8) * 8 + 16;
 }
 
-int resident_max_blocks_per_cu(size_t lds_bytes) {
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kResident), hipFuncAttributeMaxDynamicSharedMemorySize,
+int resident_max_blocks_per_cu(size_t lds_bytes, bool stop_res) {
+  const auto kernel = stop_res ? kResident<true> : kResident<false>;
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                           int(lds_bytes)) != hipSuccess) {
     (void)hipGetLastError();
     return 0;
   }
   int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kResident, RT, lds_bytes) != hipSuccess) {
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, RT, lds_bytes) != hipSuccess) {
     (void)hipGetLastError();
     return 0;
   }
@@ -587,7 +617,8 @@ int resident_max_blocks_per_cu(size_t lds_bytes) {
 }
 
 void launch_resident(const KParams& k, const ResParams& rp, hipStream_t s) {
-  hipLaunchKernelGGL(kResident, dim3(unsigned(rp.nwg)), dim3(RT), rp.lds_bytes, s, k, rp);
+  if (k.stop_res) hipLaunchKernelGGL(kResident<true>, dim3(unsigned(rp.nwg)), dim3(RT), rp.lds_bytes, s, k, rp);
+  else hipLaunchKernelGGL(kResident<false>, dim3(unsigned(rp.nwg)), dim3(RT), rp.lds_bytes, s, k, rp);
 }
 
 }  // namespace dev

@@ -145,6 +145,11 @@ class DeviceSolver {
   // Switch the convergence test on / off (drops cached graphs): the bench
   // times fixed-work steps, then solves to convergence on the same solver.
   void set_check_tol(bool on);
+  // Residual rule (Problem::stop): the absolute floor of the next solves'
+  // threshold.  The threshold lives in the device state, not in the kernels'
+  // parameters: cached graphs stay.  std::invalid_argument under the step-size
+  // rule, or for a value that is not finite and >= 0.
+  void set_atol(double atol);
   // Initial guess of the next reset() / solve() (bench: the BASELINE
   // random-init solve on the same solver as the zero-init one).
   void set_init(Init init, uint64_t seed, double amp);
@@ -206,6 +211,12 @@ class DeviceSolver {
   void enqueue_pack(int buf);   // single-sweep: y strips of buffer `buf` → send buffers
   void enqueue_unpack(int buf); // single-sweep: recv buffers → y halo columns of `buf`
   void enqueue_error();
+  // Residual rule: g_0 = h1·h2·(z⁰, r⁰) of a state read after the initial
+  // reduction, and the write of the threshold (and sqrt(g_0), for the report
+  // of a resumed solve) into the device state on the solver stream — two pad
+  // slots, DevState::red_G[1] and err[3], so a checkpoint carries them.
+  double stop_g0(const dev::DevState& s) const;
+  void enqueue_stop_threshold(double thr, double nat0);
   void enqueue_wflush();        // single-sweep: add a deferred α·p term to w (no-op if none)
   double* red_F_dev();
   double* red_G_dev();

@@ -89,6 +89,26 @@ PE_HD double shifted_diag(double D, double sigma) { return D + sigma; }
 // std::invalid_argument unless prob.shift is finite and ≥ 0 (a negative shift
 // makes the system indefinite).  Every backend calls it before any work.
 void check_shift(const Problem& prob, const char* who);
+// The breakdown test every backend makes before α = g / den exists, den =
+// h1·h2·(Ap, p), g = h1·h2·(z, r).  Step-size rule: the reference's absolute
+// |den| < 1e-15 (stage2-mpi/poisson_mpi_decomp.cpp:413), bit for bit.  Residual
+// rule: the same 1e-15 relative to g, |den| ≤ 1e-15·|g| (α beyond 1e15, or
+// den = 0).  den is of the size of g (α = O(1) for the Jacobi-scaled
+// operator), so the absolute form fires at g ≈ 1e-15 — before a threshold
+// below sqrt(g) ≈ 3e-8 can be met, which in the D⁻¹ norm (z = r / D, D ≈ 4/h²)
+// is where relative tolerances of 1e-6 lie: 2.2e-8 for F = 1 at 40×40.
+PE_HD bool cg_breakdown(double den, double g, bool res_rule) {
+  return res_rule ? fabs(den) <= 1e-15 * fabs(g) : fabs(den) < 1e-15;
+}
+// std::invalid_argument unless prob.stop is a rule, prob.atol is finite and ≥ 0,
+// and a non-zero atol comes with Stop::Residual.  Every backend, before any work.
+void check_stop(const Problem& prob, const char* who);
+// The residual rule's threshold max(tol·sqrt(g0), atol) from g0 = h1·h2·(z⁰, r⁰)
+// (one expression on every backend; a non-finite g0 gives NaN: never met).
+inline double stop_threshold(const Problem& prob, double g0) {
+  const double rel = prob.tol * std::sqrt(g0);
+  return rel < prob.atol ? prob.atol : rel;
+}
 // out = B − A w, B = rhs (null: F) at nodes inside the ellipse, 0 elsewhere
 // (assemble()'s mask).  Returns h1·h2·Σ out².  `out` may be null.
 double residual_field(const Problem& prob, const double* w, const double* rhs, double* out, int threads = 1);

@@ -29,6 +29,9 @@ namespace pe {
 
 enum class Norm : int { Weighted = 0, Unweighted = 1 };
 enum class Init : int { Zero = 0, Random = 1 };
+// Stop rule: Step — ‖w^{k+1} − w^k‖ < tol (the reference's); Residual — the
+// preconditioned residual sqrt(g_k) ≤ max(tol·sqrt(g_0), atol), g = h1·h2·(z, r).
+enum class Stop : int { Step = 0, Residual = 1 };
 
 struct Problem {
   // Box Π = [A1,B1] × [A2,B2].
@@ -45,6 +48,10 @@ struct Problem {
   // Constant shift σ ≥ 0 of the operator: (A + σI) w = B, the discrete
   // −Δu + σu = f (pe/fields.hpp).  0.0: −Δu = f, the unshifted code bit for bit.
   double shift = 0.0;
+  // Stop rule (Stop above) and, under Stop::Residual only, the absolute floor
+  // of its threshold (finite, ≥ 0; pe/fields.hpp check_stop).
+  Stop stop = Stop::Step;
+  double atol = 0.0;
 
   double h1() const { return (B1 - A1) / M; }
   double h2() const { return (B2 - A2) / N; }

@@ -112,6 +112,9 @@ struct SolveResult {
   // recurrence from w (residual replacement).
   double res_true = -1, res_rec = -1, res_gap = -1, b_norm = -1;
   int restarts = 0;
+  // Residual rule (Problem::stop; -1 otherwise): sqrt(g_0), sqrt(g_K) of the
+  // returned iterate of a converged solve, and the threshold used.
+  double res_nat0 = -1, res_nat = -1, stop_thr = -1;
   // The gradient's functionals (pe/fields.hpp), where the solve itself
   // computes them (the virtual-rank group driver on request); -1 otherwise.
   GradStats grad;

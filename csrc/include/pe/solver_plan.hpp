@@ -76,7 +76,10 @@ struct SolverPlan {
 
 // Stage one.  Refuses (std::invalid_argument) what no kernel runs, in this
 // order: the algo range, the shift (check_shift), a shift with algo >= 2, the
-// single-sweep precondition, the two-step and the three-step preconditions.
+// single-sweep precondition, the two-step and the three-step preconditions,
+// and last the residual stop rule with algo two-step / three-step (the stop
+// fields themselves, check_stop, right after the shift).  Under that rule
+// algo auto plans one iteration per launch, as PE_STEPS=1 does.
 SolverPlan plan_solver(const Problem& prob, const Block& blk, int comm_size, const SolveOptions& opt,
                        const SolverKnobs& knobs, int cus);
 // Stage two: `facts` are the occupancy figures asked with plan.ti_query / plan.order.

@@ -46,6 +46,15 @@ two-kernel iteration (``--algo auto`` or ``classic``):
 
     python -m poisson_ellipse_openmp_mpi_cuda_amd.cli --shift 40 --rhs f.npy --w0 u.npy --dump u1.npy 400 600
 
+``--stop residual`` stops on the preconditioned residual instead of the step
+size: sqrt(g_k) <= max(tol·sqrt(g_0), ``--atol``), g = h1·h2·(z, r) — the rule
+for warm starts (``--w0``) and time stepping, where a step-size test stops
+early.  ``--json`` then carries ``"stop"``, ``"atol"``, ``"res_nat0"``,
+``"res_nat"`` and ``"stop_thr"``; the device backends run one iteration per
+launch (``--algo auto``, ``classic`` or ``fused``):
+
+    python -m poisson_ellipse_openmp_mpi_cuda_amd.cli --stop residual --shift 40 --rhs f.npy --w0 u.npy --atol 1e-7 400 600
+
 Checkpoints hold the iteration state, not the fields: ``--resume`` needs the
 same ``--rhs`` (and ``--exact``) and the same ``--shift`` again, and ignores ``--w0``.
 """
@@ -94,6 +103,11 @@ def build_parser():
                          "the unshifted solve); the L2 / max error is then reported only with --exact; device backends "
                          "run --algo auto / classic; a resumed solve (--resume) needs the same --shift again")
     ap.add_argument("--tol", type=float, default=1e-6)
+    ap.add_argument("--stop", choices=("step", "residual"), default="step",
+                    help="stop rule: step (default) — the step size ||w_{k+1} - w_k|| < tol; residual — the "
+                         "preconditioned residual sqrt(g_k) <= max(tol sqrt(g_0), atol), tested before iteration k + 1")
+    ap.add_argument("--atol", type=float, default=0.0, metavar="A",
+                    help="absolute floor of the residual rule's threshold (finite, >= 0; only with --stop residual)")
     ap.add_argument("--max-iter", type=int, default=-1)
     ap.add_argument("--norm", choices=("weighted", "unweighted"), default="weighted")
     ap.add_argument("--variant", type=int, default=0, help="device arithmetic: 0 fast (default), 1 reference-exact")
@@ -130,9 +144,12 @@ def main(argv=None) -> int:
     prob.max_iter = a.max_iter
     prob.norm = a.norm
     prob.shift = a.shift
+    prob.stop = a.stop
+    prob.atol = a.atol
     want_w = bool(a.dump or a.pgm or a.dump_resid)
     try:
         prob.check_shift()
+        prob.check_stop()
         rhs = None if a.rhs is None else user_field("--rhs", np.load(a.rhs, allow_pickle=False), prob)
         w0 = None if a.w0 is None else user_field("--w0", np.load(a.w0, allow_pickle=False), prob)
         exact = None if a.exact is None else user_field("--exact", np.load(a.exact, allow_pickle=False), prob)

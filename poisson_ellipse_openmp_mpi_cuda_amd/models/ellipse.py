@@ -37,6 +37,11 @@ class EllipseProblem:
     norm: str = "weighted"  # "weighted" (stage1..4) or "unweighted" (stage0)
     # constant shift σ ≥ 0 of the operator: (A + σI) w = B, i.e. −Δu + σu = f (0.0: −Δu = f, today's code bit for bit)
     shift: float = 0.0
+    # stop rule: "step" — ‖w^{k+1} − w^k‖ < tol (the reference's, today's code bit for bit); "residual" — the
+    # preconditioned residual sqrt(g_k) <= max(tol·sqrt(g_0), atol), g = h1·h2·(z, r), tested before iteration k + 1
+    stop: str = "step"
+    # absolute floor of the residual rule's threshold (finite, >= 0; only with stop="residual")
+    atol: float = 0.0
 
     # ---- derived quantities (same formulas as csrc/include/pe/problem.hpp)
     @property
@@ -82,8 +87,24 @@ class EllipseProblem:
                              "indefinite")
         return s
 
+    def check_stop(self):
+        """(stop == "residual", atol as a float) — or ValueError: an unknown rule, an atol that is not finite
+        and >= 0, or an atol given with the step-size rule (which has none)."""
+        if self.stop not in ("step", "residual"):
+            raise ValueError(f'stop must be "step" or "residual" (got {self.stop!r})')
+        try:
+            a = float(self.atol)
+        except (TypeError, ValueError):
+            raise ValueError(f"atol must be a finite number >= 0 (got {self.atol!r})") from None
+        if not math.isfinite(a) or a < 0.0:
+            raise ValueError(f"atol must be finite and >= 0 (got {self.atol})")
+        if a != 0.0 and self.stop != "residual":
+            raise ValueError('atol belongs to stop="residual"; the step-size rule has none')
+        return self.stop == "residual", a
+
     def to_native(self):
         shift = self.check_shift()  # (before any work, on every backend)
+        res_rule, atol = self.check_stop()
         nat = native()
         p = nat.Problem()
         p.M, p.N = int(self.M), int(self.N)
@@ -95,6 +116,8 @@ class EllipseProblem:
         p.max_iter = int(self.max_iter)
         p.norm = nat.Norm.Unweighted if self.norm == "unweighted" else nat.Norm.Weighted
         p.shift = shift
+        p.stop = nat.Stop.Residual if res_rule else nat.Stop.Step
+        p.atol = atol
         return p
 
 

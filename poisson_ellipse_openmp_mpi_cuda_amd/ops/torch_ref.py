@@ -146,6 +146,16 @@ def apply_Dinv(r, D):
     return z
 
 
+def _sqrt(x: float) -> float:
+    return math.sqrt(x) if x >= 0.0 else float("nan")  # (NaN for a negative or NaN argument, as std::sqrt)
+
+
+def stop_threshold(tol: float, g0: float, atol: float = 0.0) -> float:
+    """The residual rule's threshold max(tol·sqrt(g_0), atol) — pe/fields.hpp stop_threshold, the same expression."""
+    rel = tol * _sqrt(g0)
+    return atol if rel < atol else rel
+
+
 def dot(u, v, h1, h2):
     return float((u[1:-1, 1:-1] * v[1:-1, 1:-1]).sum()) * h1 * h2
 
@@ -158,6 +168,10 @@ class TorchPCGResult:
     l2_err: float
     max_err: float
     history: list
+    # residual rule (prob.stop == "residual"; -1 otherwise): sqrt(g_0), sqrt(g_K) of a converged solve, the threshold
+    res_nat0: float = -1.0
+    res_nat: float = -1.0
+    stop_thr: float = -1.0
 
 
 def _start(prob, device, rhs, w0):
@@ -175,7 +189,10 @@ def pcg(prob: EllipseProblem, device="cpu", w0=None, max_iter: Optional[int] = N
     l2_err / max_err: against the user's `exact` when given, else against the
     analytic solution; with a user rhs, or a shifted operator (prob.shift ≠ 0:
     (A + σI) w = B, preconditioner D + σ), and no `exact` there is nothing to
-    compare with: -1."""
+    compare with: -1.  prob.stop == "residual": iterate k is tested at the top
+    of iteration k + 1, sqrt(g_k) <= max(tol·sqrt(g_0), atol) with g = h1·h2·(z, r),
+    instead of the step size after it (csrc/cpu/pcg_cpu.cpp, the same loop)."""
+    res_rule, atol = prob.check_stop()
     a, b, B = assemble(prob, device, rhs=rhs)
     h1, h2 = prob.h1, prob.h2
     sigma = prob.check_shift()
@@ -190,11 +207,18 @@ def pcg(prob: EllipseProblem, device="cpu", w0=None, max_iter: Optional[int] = N
     cap = prob.iter_cap if max_iter is None else max_iter
     hist = []
     converged = False
+    nat0 = nat = thr = -1.0
+    if res_rule:
+        nat0 = _sqrt(zr_old)
+        thr = stop_threshold(prob.tol, zr_old, atol)
     k = 0
     for k in range(1, cap + 1):
+        if res_rule and _sqrt(zr_old) <= thr:  # (a non-finite g is never met)
+            converged, nat, k = True, _sqrt(zr_old), k - 1
+            break
         Ap = apply_A(p, a, b, h1, h2, sigma)
         den = dot(Ap, p, h1, h2)
-        if abs(den) < 1e-15:
+        if (abs(den) <= 1e-15 * abs(zr_old)) if res_rule else (abs(den) < 1e-15):  # pe/fields.hpp cg_breakdown
             break
         alpha = zr_old / den
         dw = alpha * p
@@ -206,7 +230,7 @@ def pcg(prob: EllipseProblem, device="cpu", w0=None, max_iter: Optional[int] = N
         diff = math.sqrt(d2 * h1 * h2) if prob.norm == "weighted" else math.sqrt(d2)
         if keep_history:
             hist.append(diff)
-        if diff < prob.tol:
+        if not res_rule and diff < prob.tol:
             converged = True
             break
         beta = zr_new / zr_old
@@ -216,7 +240,7 @@ def pcg(prob: EllipseProblem, device="cpu", w0=None, max_iter: Optional[int] = N
         l2, mx = error_vs_analytic(prob, w, embed(prob, exact, device))
     else:
         l2, mx = error_vs_analytic(prob, w) if rhs is None and sigma == 0.0 else (-1.0, -1.0)
-    return TorchPCGResult(k, converged, w, l2, mx, hist)
+    return TorchPCGResult(k, converged, w, l2, mx, hist, nat0, nat, thr)
 
 
 @dataclass

@@ -93,6 +93,13 @@ class SolveReport:
     grad_max: float = -1.0
     # the problem's shift σ of (A + σI) w = B (to_dict() / --json carry it only when it is non-zero)
     shift: float = 0.0
+    # the stop rule and, under "residual": atol, sqrt(g_0), sqrt(g_K) of the returned iterate of a converged solve and
+    # the threshold used, g = h1·h2·(z, r) (-1: does not apply; to_dict() / --json carry the five only when stop != "step")
+    stop: str = "step"
+    atol: float = 0.0
+    res_nat0: float = -1.0
+    res_nat: float = -1.0
+    stop_thr: float = -1.0
 
     @property
     def iters_per_s(self) -> float:
@@ -107,6 +114,9 @@ class SolveReport:
         d["iters_per_s"] = self.iters_per_s
         if not d.get("shift"):
             d.pop("shift", None)
+        if d.get("stop") == "step":
+            for key in ("stop", "atol", "res_nat0", "res_nat", "stop_thr"):
+                d.pop(key, None)
         return d
 
 
@@ -236,7 +246,9 @@ def _report(backend, prob, res, ranks, threads, init, w=None, rank=0) -> SolveRe
         res_true=float(getattr(res, "res_true", -1.0)), res_rec=float(getattr(res, "res_rec", -1.0)),
         res_gap=float(getattr(res, "res_gap", -1.0)),
         b_norm=float(getattr(res, "b_norm", -1.0)), restarts=int(getattr(res, "restarts", 0)),
-        shift=float(prob.shift))
+        shift=float(prob.shift), stop=str(prob.stop), atol=float(prob.atol),
+        res_nat0=float(getattr(res, "res_nat0", -1.0)), res_nat=float(getattr(res, "res_nat", -1.0)),
+        stop_thr=float(getattr(res, "stop_thr", -1.0)))
 
 
 def _grad_mode(return_grad, on_device: bool, backend: str = "hip"):
@@ -281,13 +293,27 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
 
     ``prob.shift`` = σ > 0 (every backend) solves (A + σI) w = B, the discrete
     −Δu + σu = f, at every interior node of the box, with the preconditioner
-    D + σ; the stop rule, norms and statuses are unchanged.  The analytic
+    D + σ; the stop rules, norms and statuses are unchanged.  The analytic
     solution does not apply: ``l2_err`` / ``max_err`` are −1 unless ``exact``
     is given.  The device backends run the classic two-kernel path (``algo``
     "auto" or "classic"; the single-sweep kernels refuse a shift with
     ValueError).  A resumed solve needs the same shift again: checkpoints do
     not hold it.  σ must be finite and ≥ 0 (ValueError); 0 is today's solve
     bit for bit.
+
+    ``prob.stop`` = "residual" (every backend) stops on the preconditioned
+    residual instead of the step size: with g_k = h1·h2·Σ z_k·r_k, z = D⁻¹r —
+    the scalar the recurrence forms for β anyway — iterate k is tested at the
+    top of iteration k + 1, sqrt(g_k) <= max(``tol``·sqrt(g_0), ``atol``), and
+    the solve ends converged with ``iters`` = k (0 for a ``w0`` that already
+    meets it: ``w0`` comes back unchanged).  The iteration cap wins: the
+    ``max_iter``-th iterate is not tested.  The report carries ``res_nat0`` =
+    sqrt(g_0), ``res_nat`` = sqrt(g_K) and ``stop_thr``; ``last_diff`` /
+    ``history`` still hold step sizes.  A time stepper passes ``atol`` =
+    ``tol``·``res_nat0`` of its first step to the later, warm-started ones.  The
+    device backends run one iteration per launch under it (classic, the
+    resident kernel or the single sweep; ``algo`` "two-step" / "three-step"
+    refuse with ValueError).  "step", the default, is the reference's rule.
 
     ``exact`` (every backend, same form): the solution to report the error
     against — a manufactured solution u with ``rhs`` = −Δu, say.  Then
@@ -369,7 +395,9 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
         rep = SolveReport("torch", prob.M, prob.N, 1, 1, 1, 1, r.iters, r.converged, False,
                           r.history[-1] if r.history else 0.0, timers, r.l2_err, r.max_err, -1.0,
                           "zero" if w0 is None else "field",
-                          r.w[1:-1, 1:-1].cpu().numpy() if return_w else None, shift=float(prob.shift))
+                          r.w[1:-1, 1:-1].cpu().numpy() if return_w else None, shift=float(prob.shift),
+                          stop=str(prob.stop), atol=float(prob.atol), res_nat0=r.res_nat0, res_nat=r.res_nat,
+                          stop_thr=r.stop_thr)
         if grad:
             g, *stats = torch_ref.gradient(prob, r.w)
             _set_grad(rep, stats, g.cpu().numpy() if grad is True else None)
@@ -556,16 +584,26 @@ class DeviceSession:
         self.close()
         return False
 
-    def solve(self, rhs=None, w0=None, exact=None, return_w=False, return_grad=False) -> SolveReport:
+    def solve(self, rhs=None, w0=None, exact=None, return_w=False, return_grad=False, atol=None) -> SolveReport:
         """One solve on the kept solver.  ``rhs`` / ``w0`` / ``exact``: host
         arrays or GPU tensors of the global interior, per call and mixed
         freely; None clears a field back to F / ``init`` / the analytic error.  ``return_w``: False, True (numpy; on a
         multi-process job gathered onto rank 0) or "device" (a float64 GPU
         tensor written by the solver; on a multi-process job this rank's block,
         its position in the report's ``w_origin``).  ``return_grad``: False,
-        "stats", True or "device", as in solve()."""
+        "stats", True or "device", as in solve().  ``atol`` (``stop="residual"``
+        only): the absolute floor of the threshold from this solve on — the
+        session's problem takes it; the kept solver, and any graph it has
+        captured, stay as they are (the threshold lives in device memory)."""
         if isinstance(return_w, str) and return_w != "device":
             raise ValueError('return_w must be True, False or "device"')
+        if atol is not None:
+            prob = dataclasses.replace(self.prob, atol=atol)
+            prob.check_stop()  # (ValueError before anything is set)
+            if self.solver is None:
+                raise RuntimeError("DeviceSession is closed")
+            self.solver.set_atol(float(atol))
+            self.prob = prob
         grad = _grad_mode(return_grad, True)
         return self._solve(_field_arg("rhs", rhs, self.prob, True), _field_arg("w0", w0, self.prob, True), return_w,
                            _field_arg("exact", exact, self.prob, True), grad)
