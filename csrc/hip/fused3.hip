@@ -86,6 +86,9 @@ static_assert(HL3 >= H3 && HR3 >= H3, "three-step strip: 64 loaded columns (one 
 #ifndef PE_S3_NTX
 #define PE_S3_NTX 0  // 1: non-temporal loads of r and p (experiment)
 #endif
+#ifndef PE_S3_BPRIO
+#define PE_S3_BPRIO 0  // 1: raised issue priority (s_setprio 1) while a wave marches a band item (experiment)
+#endif
 constexpr int kS3XD = PE_S3_XD, kS3WD = PE_S3_WD;
 static_assert(6 % kS3XD == 0 && 6 % kS3WD == 0, "register ring periods must divide the 6-step group");
 constexpr int NS = kNS3;
@@ -450,6 +453,16 @@ struct Pre3 {
   bool staged;  // its first r / p / w rows were sent into the wave's LDS (stage_first3)
 };
 
+// A band item's row state, carried from step to step in scalars.  sl: the face
+// ring's slots (7 rows t-6 .. t against the 6-step group: runtime values),
+// renamed rather than recomputed — at step JJ of a group row t-d is in
+// sl[(d - JJ) mod 7], and the group's end rotates the array by one.  gen: bit
+// d is the gen flag of row t-d, shifted in when the row enters (stage A).
+struct M3Band {
+  int sl[kRing3];
+  unsigned gen;
+};
+
 template <bool STEADY>
 __device__ __forceinline__ URow urow(const M3Ctx& c, int q) {
   URow r{c.ih1, c.ih2, c.dcl};
@@ -513,12 +526,13 @@ __device__ __forceinline__ void push_row3(const KParams& k, const M3Ctx& c, M3Ri
 }
 
 // One row step of the march: stage A at row t = t0 + n, B..G at rows
-// t-1..t-6.  JJ = n mod 6 fixes the register ring slots at compile time; bs
-// is the band face-ring slot of row t.  STEADY (uniform items): every stage
-// row lies inside the item — no row tests, no clamped loads.
+// t-1..t-6.  JJ = n mod 6 fixes the register ring slots at compile time; bd
+// holds the band face-ring slots and gen flags of rows t-6 .. t.  STEADY
+// (uniform and band items): every stage row lies inside the item — no row
+// tests, no clamped loads.
 template <int KIND, bool PUSH, bool EDGE, bool STEADY, int JJ>
 __device__ __forceinline__ void step3(const KParams& k, const M3Ctx& c, M3Rings& x, M3Ptr& rp, const RowCtx& rx,
-                                      WaveTV3& tvw, double (&sv)[NS], int n, int bs) {
+                                      WaveTV3& tvw, double (&sv)[NS], int n, M3Band& bd) {
   constexpr bool BAND = KIND == kBand, UNI = KIND == kUniform;
   constexpr int XD = kS3XD, WD = kS3WD;
   const double zc1 = c.zc1, zc2 = c.zc2, zc3 = c.zc3, w1 = c.w1, w2 = c.w2, w3 = c.w3;
@@ -545,16 +559,18 @@ __device__ __forceinline__ void step3(const KParams& k, const M3Ctx& c, M3Rings&
   // pipeline fill: stage d (B = 1 … F = 5) first feeds a needed row at step
   // 2d (G's rows are tested by inr): skip it before — its rows are never used
   auto live = [&](int d) { return STEADY || n >= 2 * d; };
-  // band ring slots (runtime, mod 7) of rows t .. t-6
+  // band ring slots of rows t .. t-6 (M3Band)
   int bsl[7];
 #pragma unroll
-  for (int d = 0; d < 7; ++d) bsl[d] = bs >= d ? bs - d : bs - d + kRing3;
+  for (int d = 0; d < 7; ++d) bsl[d] = bd.sl[(d - JJ + kRing3) % kRing3];
+  // gen flag of row t-d (stage A shifts row t's in first)
+  auto gen = [&](int d) { return ((bd.gen >> d) & 1u) != 0; };
   // masked products z = D⁻¹·v (0 at global-boundary rows / columns)
   auto zmask = [&](int q, double v, double d) -> double {
     if constexpr (UNI) {  // d: the row scalar (interior rows folded in)
       return EDGE ? (v * d) * c.lf0 : v * d;
     } else {
-      return (interior(q) && c.lv0) ? v * d : 0.0;
+      return ((STEADY || interior(q)) && c.lv0) ? v * d : 0.0;
     }
   };
   // the operator at row q (band ring slots sl, sln) and 1/D of the node
@@ -563,8 +579,10 @@ __device__ __forceinline__ void step3(const KParams& k, const M3Ctx& c, M3Rings&
       const URow r = urow<STEADY>(c, q);
       d = r.d;
       return lapu(r, um, u0, un);
+    } else if constexpr (BAND) {
+      return apply_ring1(k, tvw, gen(t - q), sl, sln, um, u0, un, d);
     } else {
-      return apply_row1<BAND>(k, rx, tvw, q, c0, sl, sln, um, u0, un, d);
+      return apply_row1<false>(k, rx, tvw, q, c0, sl, sln, um, u0, un, d);
     }
   };
   // p_i = zc·z + β·p_{i-1}.  Under fast contraction either product may become
@@ -574,9 +592,11 @@ __device__ __forceinline__ void step3(const KParams& k, const M3Ctx& c, M3Rings&
   // (tests/test_sweep_pins.py): zc·z rounded, then β·p added fused — except in
   // stage A of the steady groups' last steps (from JJ = 4 on interior strips,
   // JJ = 3 in the push variant on every strip), where β·p is the rounded one.
+  // The lane-tested kinds rounded zc·z at every site of every instantiation
+  // when the band march's outputs were pinned (tests/test_band_pins.py).
   auto pnext = [&](double zc, double z, double b, double p, bool zfused) -> double {
     if constexpr (UNI) return zfused ? __builtin_fma(zc, z, b * p) : __builtin_fma(b, p, zc * z);
-    else return zc * z + b * p;
+    else return __builtin_fma(b, p, zc * z);
   };
   constexpr bool kAzf = STEADY && (PUSH ? JJ >= 3 : (!EDGE && JJ >= 4));
   // ---- A: row t ----
@@ -603,7 +623,11 @@ __device__ __forceinline__ void step3(const KParams& k, const M3Ctx& c, M3Rings&
   {
     double d;
     if constexpr (UNI) d = urow<STEADY>(c, t).d;
-    else d = BAND ? enter_band1(k, rx, tvw, t, c0, bsl[0]) : dinv_plain1(k, rx, t, c0);
+    else if constexpr (BAND) {
+      bool g;
+      d = enter_band1(k, rx, tvw, t, c0, bsl[0], g);
+      bd.gen = (bd.gen << 1) | (g ? 1u : 0u);
+    } else d = dinv_plain1(k, rx, t, c0);
     const double z = zmask(t, rin, d);
     x.P1[m0] = pnext(zc1, z, c.b1, pin, kAzf);
     x.RI[e0] = rin;
@@ -739,12 +763,10 @@ __device__ __forceinline__ void step3(const KParams& k, const M3Ctx& c, M3Rings&
 // work into this one.
 template <int KIND, bool PUSH, bool EDGE, bool STEADY>
 __device__ __forceinline__ void group3(const KParams& k, const M3Ctx& c, M3Rings& x, M3Ptr& rp, const RowCtx& rx,
-                                       WaveTV3& tvw, double (&sv)[NS], int n0, int nsteps, int& bs) {
-  auto adv = [&]() { bs = bs == kRing3 - 1 ? 0 : bs + 1; };
+                                       WaveTV3& tvw, double (&sv)[NS], int n0, int nsteps, M3Band& bd) {
 #define PE_STEP3(JJ)                                                              \
   if (STEADY || n0 + JJ < nsteps) {                                               \
-    step3<KIND, PUSH, EDGE, STEADY, JJ>(k, c, x, rp, rx, tvw, sv, n0 + JJ, bs);   \
-    adv();                                                                        \
+    step3<KIND, PUSH, EDGE, STEADY, JJ>(k, c, x, rp, rx, tvw, sv, n0 + JJ, bd);   \
     if (STEADY) __builtin_amdgcn_sched_barrier(0);                                \
   }
   PE_STEP3(0)
@@ -754,6 +776,12 @@ __device__ __forceinline__ void group3(const KParams& k, const M3Ctx& c, M3Rings
   PE_STEP3(4)
   PE_STEP3(5)
 #undef PE_STEP3
+  if constexpr (KIND == kBand) {  // six rows on: row t-d is where row t-d-1 was
+    const int s0 = bd.sl[0];
+#pragma unroll
+    for (int i = 0; i + 1 < kRing3; ++i) bd.sl[i] = bd.sl[i + 1];
+    bd.sl[kRing3 - 1] = s0;
+  }
 }
 
 // The item march (one strip × rows ib..ie), accumulating this wave's sums.
@@ -888,7 +916,10 @@ __device__ __forceinline__ void march3(const KParams& k, const Coef3& cf, bool f
 
   const int nsteps = ie + H3 - c.t0 + 1;
   const int rows = ie - ib + 1;
-  int bs = 0;  // band ring slot of row t: (t - t0) mod 7
+  M3Band bd;  // row t0 + n in ring slot n mod 7: row t0 in slot 0, the (never entered) rows before it below
+  bd.gen = 0;
+#pragma unroll
+  for (int i = 0; i < kRing3; ++i) bd.sl[i] = i == 0 ? 0 : kRing3 - i;
   int sg = 3;  // (SST: next step-stamp slot)
   if constexpr (SST) {
     if (sst && lane == 0) sst[2] = rtc3();
@@ -900,7 +931,7 @@ __device__ __forceinline__ void march3(const KParams& k, const Coef3& cf, bool f
     }
     prio_turn(k);
   };
-  // steady groups (uniform items): stage rows t-6 .. t and the prefetched
+  // steady groups (uniform and band items): stage rows t-6 .. t and the prefetched
   // rows inside the item for all six steps (n ≥ 12, n ≤ rows + 4); the fill
   // and drain groups around them test rows.  Three loops, not one with a
   // branch: the merged ring state would cost a copy of every ring.
@@ -916,25 +947,34 @@ __device__ __forceinline__ void march3(const KParams& k, const Coef3& cf, bool f
   rp.xi = nullptr;
   rp.yo = rp.wo = nullptr;
   int n0 = 0;
-  const int nsteady_end = KIND == kUniform ? rows + 4 - 5 : -1;  // last steady group start
+  constexpr bool kSteady = KIND == kUniform || KIND == kBand;
+  const int nsteady_end = kSteady ? rows + 4 - 5 : -1;  // last steady group start
   for (; n0 < nsteps && !(n0 >= 12 && n0 <= nsteady_end); n0 += 6) {
     reload(n0);
-    group3<KIND, PUSH, EDGE, false>(k, c, x, rp, rx, tvw, sv, n0, nsteps, bs);
+    group3<KIND, PUSH, EDGE, false>(k, c, x, rp, rx, tvw, sv, n0, nsteps, bd);
     sstamp();
   }
-  if constexpr (KIND == kUniform) {
+  if constexpr (kSteady) {
     // the steady groups' row bases, at the first steady step's rows
     rp.xi = (const gchar3*)(c.Xm + int64_t(c.t0 + n0 + XD) * c.pitch);
     rp.yo = (gchar3*)(c.Ym + int64_t(c.t0 + n0 - 3) * c.pitch);
     rp.wo = (gchar3*)(c.Wm + int64_t(c.t0 + n0 - 2) * c.wp);
+    // (the uniform steady loop's own copies of the scalars it reads every
+    // step: live ranges that end with the loop, so the allocator keeps them in
+    // SGPRs there whatever the rest of the kernel spills)
+    M3Ctx cs = c;
+    if constexpr (KIND == kUniform) {
+      asm("" : "+s"(cs.a1), "+s"(cs.a2), "+s"(cs.a3), "+s"(rp.wb), "+s"(rp.pb));
+      if constexpr (PUSH || SST) asm("" : "+s"(cs.zc1), "+s"(cs.zc2), "+s"(cs.zc3), "+s"(cs.b1), "+s"(cs.b2), "+s"(cs.b3));
+    }
     for (; n0 <= nsteady_end; n0 += 6) {
       reload(n0);
-      group3<KIND, PUSH, EDGE, true>(k, c, x, rp, rx, tvw, sv, n0, nsteps, bs);
+      group3<KIND, PUSH, EDGE, true>(k, cs, x, rp, rx, tvw, sv, n0, nsteps, bd);
       sstamp();
     }
     for (; n0 < nsteps; n0 += 6) {
       reload(n0);
-      group3<KIND, PUSH, EDGE, false>(k, c, x, rp, rx, tvw, sv, n0, nsteps, bs);
+      group3<KIND, PUSH, EDGE, false>(k, c, x, rp, rx, tvw, sv, n0, nsteps, bd);
       sstamp();
     }
   }
@@ -1071,7 +1111,9 @@ __device__ __forceinline__ void walk3(const KParams& k, const Coef3& cf, bool fi
         for (int i = ln; i < kRing3 * 64; i += 64) (&tv.d0r[0][0])[i] = 0.0;
         ring_zeroed = true;
       }
+      if (PE_S3_BPRIO) __builtin_amdgcn_s_setprio(1);
       march3<kBand, PUSH, true, STAMP>(k, cf, fix, par, s, ib, ie, tv, acc, sst, pre, p1);
+      if (PE_S3_BPRIO) __builtin_amdgcn_s_setprio(0);
     } else if (e.x & kUniBit) {
       // edge strips (a global-boundary or padding column in the window) mask z
       const int c0 = -(HL3 - 1) + s * FSW3 + int(threadIdx.x & 63);

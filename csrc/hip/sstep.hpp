@@ -243,10 +243,13 @@ __device__ __forceinline__ void row_in1(const RowCtx& rx, int q, int c0, bool& i
 }
 
 // First stage of a band item: row q's faces into ring slot `sl`; returns 1/D.
+// gen: the row holds a boundary-band node in the strip's window (wave-uniform;
+// the stages that follow read it from the caller instead of the row classes).
 template <class WT>
-__device__ __forceinline__ double enter_band1(const KParams& k, const RowCtx& rx, WT& tv, int q, int c0, int sl) {
+__device__ __forceinline__ double enter_band1(const KParams& k, const RowCtx& rx, WT& tv, int q, int c0, int sl,
+                                              bool& gen) {
   const int lane = threadIdx.x & 63;
-  bool in0, gen;
+  bool in0;
   row_in1(rx, q, c0, in0, gen);
   double d, a0, b0;
   if (gen) {
@@ -292,6 +295,28 @@ __device__ __forceinline__ double apply_row1(const KParams& k, const RowCtx& rx,
   }
   d = in0 ? k.dinv_in : k.dinv_out;
   return lap(k, in0 ? 1.0 : k.inv_eps, um, u0, un, ul, ur);
+}
+
+// The same operator at a row of a band item from what the row's entry left in
+// ring slot sl (enter_band1 stores a0, b0 and 1/D of EVERY row, gen or not):
+// a row that is not gen has one face coefficient per column, a0 — the
+// 1 / 1/ε that apply_row1 selects from the row's interior interval — so no
+// stage reads the row classes again.  gen: the row's flag as enter_band1
+// returned it.  Same expression trees as apply_row1<true>.
+template <class WT>
+__device__ __forceinline__ double apply_ring1(const KParams& k, const WT& tv, bool gen, int sl, int sln, double um,
+                                              double u0, double un, double& d) {
+  const int lane = threadIdx.x & 63;
+  const double ul = dpp_shr1(u0), ur = dpp_shl1(u0);
+  if (gen) {
+    const double a0 = tv.a0r[sl][lane], a1 = tv.a0r[sln][lane];
+    const double b0 = tv.b0r[sl][lane], b1 = tv.b0r[sl][lane + 1];
+    const CS x0{a0, a1, b0, b1, k.dring ? tv.d0r[sl][lane] : dinv_faces(k, a0, a1, b0, b1)};
+    d = x0.d;
+    return stencil<false>(k, x0, um, u0, un, ul, ur);
+  }
+  d = tv.d0r[sl][lane];
+  return lap(k, tv.a0r[sl][lane], um, u0, un, ul, ur);
 }
 
 // Row scalars of a uniform row (fused3.hip uniform items):
