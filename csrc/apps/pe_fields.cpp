@@ -2,8 +2,9 @@
 // value encodes (i, j) and checks it node by node — the owned parts tile the
 // interior, the rings hold the neighbours' values and zeros on the box
 // boundary.  Then pe::gradient_field, pe::apply_operator and
-// pe::residual_field (unshifted and with Problem::shift) on two small grids
-// against their definitions written out.  No device: the sanitizer build's driver of pe/fields.hpp (make asan).
+// pe::residual_field (unshifted, with Problem::shift and with a reaction
+// field, whose ring-1 slices are checked too) on two small grids against their
+// definitions written out.  No device: the sanitizer build's driver of pe/fields.hpp (make asan).
 //   pe_fields M N PX PY
 #include <algorithm>
 #include <cmath>
@@ -64,7 +65,11 @@ static int64_t check_gradient(const pe::Problem& P) {
 // field that is non-zero everywhere; one and three threads, with and without
 // a destination, built-in F and a user right-hand side; the unshifted operator
 // and A + σI for two shifts (A_σ v = (Ax + Ay) + σ·v written out), and the
-// refusal of a negative or non-finite shift.
+// refusal of a negative or non-finite shift; then A + diag(c) for a reaction
+// field c with zeros ((Ax + Ay) + c_ij·v written out), its refusals (a negative
+// or non-finite entry, the flag without the field and the reverse, a field
+// together with a shift) and its ring-1 slices on 2 × 2 blocks, the device
+// plane's form.
 static int64_t check_operator(const pe::Problem& P0) {
   const pe::Problem& P = P0;
   const int64_t M = P.M, N = P.N, gny = N - 1, n = (M - 1) * gny, C = N + 2;
@@ -93,10 +98,55 @@ static int64_t check_operator(const pe::Problem& P0) {
     } catch (const std::invalid_argument&) {
     }
   }
-  for (const double sigma : {0.0, 0.75, 40.0})
+  // the reaction field: 0 .. 35 in steps of 3.5, exact zeros on every eleventh node
+  std::vector<double> cr(v.size());
+  auto cval = [&](int64_t i, int64_t j) {
+    return (i < 1 || i > M - 1 || j < 1 || j > N - 1) ? 0.0 : 3.5 * double((i * 7 + j * 13) % 11);
+  };
+  for (int64_t i = 1; i < M; ++i)
+    for (int64_t j = 1; j < N; ++j) cr[size_t((i - 1) * gny + (j - 1))] = cval(i, j);
+  {
+    pe::Problem R = P0, S = P0;
+    R.reaction = true;
+    S.reaction = true;
+    S.shift = 1.0;
+    std::vector<double> neg = cr, nan = cr, inf = cr;
+    neg[3] = -1e-300;
+    nan[3] = std::nan("");
+    inf[3] = HUGE_VAL;
+    auto refused = [&](const pe::Problem& Q, const double* c) {
+      try {
+        pe::apply_operator(Q, v.data(), nullptr, 1, c);
+        pe::residual_field(Q, v.data(), nullptr, nullptr, 1, c);
+        return false;
+      } catch (const std::invalid_argument&) {
+        return true;
+      }
+    };
+    for (const double* c : {neg.data(), nan.data(), inf.data()})
+      if (!refused(R, c)) ++bad;
+    if (!refused(R, nullptr) || !refused(P0, cr.data()) || !refused(S, cr.data())) ++bad;
+    if (M > 2 && N > 2) {  // ring-1 slices: the neighbours' values, zeros on the box boundary
+      pe::ProcessGrid pg;
+      pg.Px = pg.Py = 2;
+      for (int r = 0; r < 4; ++r) {
+        const pe::Block blk = pe::decompose(int(M), int(N), pg, r);
+        const std::vector<double> ring = pe::block_field(cr.data(), int(M), int(N), blk, 1);
+        if (int64_t(ring.size()) != (blk.nx + 2) * (blk.ny + 2)) ++bad;
+        for (int64_t li = 0; li <= blk.nx + 1; ++li)
+          for (int64_t lj = 0; lj <= blk.ny + 1; ++lj)
+            if (ring[size_t(li * (blk.ny + 2) + lj)] != cval(blk.i0 - 1 + li, blk.j0 - 1 + lj)) ++bad;
+      }
+    }
+  }
+  for (const int kind : {0, 1, 2, 3})  // σ = 0, 0.75, 40; 3: the reaction field
   for (int mode = 0; mode < 3; ++mode) {  // 0: A v; 1: F − A v; 2: f − A v
     pe::Problem P = P0;
+    const bool field = kind == 3;
+    const double sigma = kind == 1 ? 0.75 : kind == 2 ? 40.0 : 0.0;
     P.shift = sigma;
+    P.reaction = field;
+    const double* creact = field ? cr.data() : nullptr;
     const double* rhs = mode == 2 ? f.data() : nullptr;
     std::vector<double> want(v.size());
     double s = 0.0;
@@ -106,7 +156,8 @@ static int64_t check_operator(const pe::Problem& P0) {
         const double Ax = -1.0 / h1 * (a[size_t(c + C)] * (V[size_t(c + C)] - V[size_t(c)]) / h1 - a[size_t(c)] * (V[size_t(c)] - V[size_t(c - C)]) / h1);
         const double Ay = -1.0 / h2 * (b[size_t(c + 1)] * (V[size_t(c + 1)] - V[size_t(c)]) / h2 - b[size_t(c)] * (V[size_t(c)] - V[size_t(c - 1)]) / h2);
         double r = Ax + Ay;
-        if (sigma != 0.0) r = r + sigma * V[size_t(c)];
+        if (field) r = r + cr[size_t(o)] * V[size_t(c)];  // (every node, c = 0 included)
+        else if (sigma != 0.0) r = r + sigma * V[size_t(c)];
         if (mode) {
           const bool in = pe::in_ellipse(P.A1 + i * h1, P.A2 + j * h2, P.cx, P.cy);
           r = (in ? (rhs ? rhs[size_t(o)] : P.F) : 0.0) - r;
@@ -116,8 +167,10 @@ static int64_t check_operator(const pe::Problem& P0) {
       }
     for (int T : {1, 3}) {
       std::vector<double> got(v.size(), -7.0);
-      const double sum = mode ? pe::residual_field(P, v.data(), rhs, got.data(), T) : pe::apply_operator(P, v.data(), got.data(), T);
-      const double only = mode ? pe::residual_field(P, v.data(), rhs, nullptr, T) : pe::apply_operator(P, v.data(), nullptr, T);
+      const double sum = mode ? pe::residual_field(P, v.data(), rhs, got.data(), T, creact)
+                              : pe::apply_operator(P, v.data(), got.data(), T, creact);
+      const double only = mode ? pe::residual_field(P, v.data(), rhs, nullptr, T, creact)
+                               : pe::apply_operator(P, v.data(), nullptr, T, creact);
       if (got != want || only != sum) ++bad;
       if (T == 1 ? sum != h1 * h2 * s : std::fabs(sum - h1 * h2 * s) > 1e-12 * std::fabs(h1 * h2 * s)) ++bad;
     }
@@ -175,7 +228,8 @@ int main(int argc, char** argv) {
   const int64_t gbad = check_gradient(ref) + check_gradient(tiny);
   std::printf("pe_fields gradient_field 10x50, 12x12 (cx = cy = 30): %s\n", gbad ? "MISMATCH" : "ok");
   const int64_t obad = check_operator(ref) + check_operator(tiny);
-  std::printf("pe_fields apply_operator / residual_field 10x50, 12x12 (cx = cy = 30), shift 0, 0.75, 40: %s\n",
+  std::printf("pe_fields apply_operator / residual_field 10x50, 12x12 (cx = cy = 30), shift 0, 0.75, 40 and a reaction "
+              "field: %s\n",
               obad ? "MISMATCH" : "ok");
   return bad || gbad || obad ? 1 : 0;
 }

@@ -156,6 +156,7 @@ PYBIND11_MODULE(_native, m) {
       .def_readwrite("shift", &Problem::shift)
       .def_readwrite("stop", &Problem::stop)
       .def_readwrite("atol", &Problem::atol)
+      .def_readwrite("reaction", &Problem::reaction)
       .def("h1", &Problem::h1)
       .def("h2", &Problem::h2)
       .def("eps", &Problem::eps)
@@ -265,12 +266,13 @@ PYBIND11_MODULE(_native, m) {
   m.def(
       "cpu_solve_grid",
       [](const Problem& P, const ProcessGrid& pg, const SolveOptions& opt, bool return_w, py::object rhs,
-         py::object w0, py::object exact) {
-        FieldArr hr, hw, he;
+         py::object w0, py::object exact, py::object reaction) {
+        FieldArr hr, hw, he, hc;
         UserFields uf;
         uf.rhs = field_ptr(rhs, P.M - 1, P.N - 1, "rhs", hr);
         uf.w0 = field_ptr(w0, P.M - 1, P.N - 1, "w0", hw);
         uf.exact = field_ptr(exact, P.M - 1, P.N - 1, "exact", he);
+        uf.reaction = field_ptr(reaction, P.M - 1, P.N - 1, "reaction", hc);
         std::vector<double> w;
         SolveResult r;
         {
@@ -282,7 +284,8 @@ PYBIND11_MODULE(_native, m) {
         return py::make_tuple(r, wa);
       },
       py::arg("prob"), py::arg("grid"), py::arg("opt") = SolveOptions(), py::arg("return_w") = false,
-      py::arg("rhs") = py::none(), py::arg("w0") = py::none(), py::arg("exact") = py::none());
+      py::arg("rhs") = py::none(), py::arg("w0") = py::none(), py::arg("exact") = py::none(),
+      py::arg("reaction") = py::none());
 
   // One rank of a multi-process CPU run; the transport is Python callbacks
   // (torch.distributed, typically gloo).  exchange_fn receives a list of
@@ -291,12 +294,13 @@ PYBIND11_MODULE(_native, m) {
       "cpu_solve_rank",
       [](const Problem& P, const Block& blk, py::function reduce_fn, py::function exchange_fn,
          py::function barrier_fn, const SolveOptions& opt, bool return_w, py::object rhs, py::object w0,
-         py::object exact) {
-        FieldArr hr, hw, he;
+         py::object exact, py::object reaction) {
+        FieldArr hr, hw, he, hc;
         UserFields uf;  // the GLOBAL arrays: every rank passes the same and takes its slice
         uf.rhs = field_ptr(rhs, P.M - 1, P.N - 1, "rhs", hr);
         uf.w0 = field_ptr(w0, P.M - 1, P.N - 1, "w0", hw);
         uf.exact = field_ptr(exact, P.M - 1, P.N - 1, "exact", he);
+        uf.reaction = field_ptr(reaction, P.M - 1, P.N - 1, "reaction", hc);
         auto reduce = [reduce_fn](double* buf, int n, bool is_max) {
           py::gil_scoped_acquire g;
           py::array_t<double> a({n}, {int64_t(sizeof(double))}, buf, py::none());
@@ -329,7 +333,7 @@ PYBIND11_MODULE(_native, m) {
       },
       py::arg("prob"), py::arg("block"), py::arg("reduce_fn"), py::arg("exchange_fn"), py::arg("barrier_fn"),
       py::arg("opt") = SolveOptions(), py::arg("return_w") = false, py::arg("rhs") = py::none(),
-      py::arg("w0") = py::none(), py::arg("exact") = py::none());
+      py::arg("w0") = py::none(), py::arg("exact") = py::none(), py::arg("reaction") = py::none());
 
   // One block's slices of global interior arrays (pe/fields.hpp block_field):
   // (rhs owned nx × ny | None, w0 with its ring (nx+2) × (ny+2) | None) — the
@@ -383,25 +387,27 @@ PYBIND11_MODULE(_native, m) {
   // h1·h2·Σ v·(A v), or h1·h2·Σ (B − A w)².
   m.def(
       "apply_operator",
-      [](const Problem& P, py::object v, bool field, int threads) {
-        FieldArr h;
+      [](const Problem& P, py::object v, bool field, int threads, py::object reaction) {
+        FieldArr h, hc;
         const double* p = field_ptr(v, int64_t(P.M) - 1, int64_t(P.N) - 1, "v", h);
         if (!p) throw std::invalid_argument("apply_operator: the array is None");
+        const double* c = field_ptr(reaction, int64_t(P.M) - 1, int64_t(P.N) - 1, "reaction", hc);
         std::vector<double> out(field ? size_t((int64_t(P.M) - 1) * (int64_t(P.N) - 1)) : 0);
         double sum;
         {
           py::gil_scoped_release nogil;
-          sum = apply_operator(P, p, field ? out.data() : nullptr, threads);
+          sum = apply_operator(P, p, field ? out.data() : nullptr, threads, c);
         }
         py::object oa = py::none();
         if (field) oa = to_array(std::move(out), P.M - 1, P.N - 1);
         return py::make_tuple(sum, oa);
       },
-      py::arg("prob"), py::arg("v"), py::arg("field") = true, py::arg("threads") = 1);
+      py::arg("prob"), py::arg("v"), py::arg("field") = true, py::arg("threads") = 1, py::arg("reaction") = py::none());
   m.def(
       "residual_field",
-      [](const Problem& P, py::object w, py::object rhs, bool field, int threads) {
-        FieldArr h, hr;
+      [](const Problem& P, py::object w, py::object rhs, bool field, int threads, py::object reaction) {
+        FieldArr h, hr, hc;
+        const double* c = field_ptr(reaction, int64_t(P.M) - 1, int64_t(P.N) - 1, "reaction", hc);
         const double* p = field_ptr(w, int64_t(P.M) - 1, int64_t(P.N) - 1, "w", h);
         if (!p) throw std::invalid_argument("residual_field: the array is None");
         const double* r = field_ptr(rhs, int64_t(P.M) - 1, int64_t(P.N) - 1, "rhs", hr);
@@ -409,13 +415,14 @@ PYBIND11_MODULE(_native, m) {
         double sum;
         {
           py::gil_scoped_release nogil;
-          sum = residual_field(P, p, r, field ? out.data() : nullptr, threads);
+          sum = residual_field(P, p, r, field ? out.data() : nullptr, threads, c);
         }
         py::object oa = py::none();
         if (field) oa = to_array(std::move(out), P.M - 1, P.N - 1);
         return py::make_tuple(sum, oa);
       },
-      py::arg("prob"), py::arg("w"), py::arg("rhs") = py::none(), py::arg("field") = true, py::arg("threads") = 1);
+      py::arg("prob"), py::arg("w"), py::arg("rhs") = py::none(), py::arg("field") = true, py::arg("threads") = 1,
+      py::arg("reaction") = py::none());
 
   m.def("host_coefficients", [](const Problem& P, const Block& blk) {
     std::vector<double> a, b;
@@ -738,6 +745,22 @@ PYBIND11_MODULE(_native, m) {
           py::arg("ptr"), py::arg("stride_i"), py::arg("stride_j"), py::arg("f32") = false, py::arg("stream") = 0,
           "the initial guess as the GLOBAL (M-1) × (N-1) array in device memory (see set_rhs_device)")
       .def(
+          "set_reaction",
+          [](DeviceSolver& s, py::object ringed) {
+            FieldArr h;
+            s.set_reaction(field_ptr(ringed, s.block().nx + 2, s.block().ny + 2, "reaction", h));
+          },
+          py::arg("ringed"),
+          "this block's (nx+2) × (ny+2) slice of the reaction field with its ring (block_field ring 1); a solver "
+          "constructed with Problem.reaction only, None refused")
+      .def(
+          "set_reaction_device",
+          [](DeviceSolver& s, uintptr_t ptr, int64_t si, int64_t sj, bool f32, uintptr_t stream) {
+            s.set_reaction_device(reinterpret_cast<const void*>(ptr), si, sj, f32, reinterpret_cast<hipStream_t>(stream));
+          },
+          py::arg("ptr"), py::arg("stride_i"), py::arg("stride_j"), py::arg("float32") = false, py::arg("stream") = 0,
+          "the reaction field as the GLOBAL (M-1) × (N-1) array in device memory (see set_rhs_device)")
+      .def(
           "set_exact",
           [](DeviceSolver& s, py::object owned) {
             FieldArr h;
@@ -1034,12 +1057,13 @@ PYBIND11_MODULE(_native, m) {
   m.def(
       "device_solve_group_grid",
       [](const Problem& P, const ProcessGrid& pg, const SolveOptions& opt, bool return_w, py::object rhs,
-         py::object w0, py::object exact) {
-        FieldArr hr, hw, he;
+         py::object w0, py::object exact, py::object reaction) {
+        FieldArr hr, hw, he, hc;
         UserFields uf;
         uf.rhs = field_ptr(rhs, P.M - 1, P.N - 1, "rhs", hr);
         uf.w0 = field_ptr(w0, P.M - 1, P.N - 1, "w0", hw);
         uf.exact = field_ptr(exact, P.M - 1, P.N - 1, "exact", he);
+        uf.reaction = field_ptr(reaction, P.M - 1, P.N - 1, "reaction", hc);
         std::vector<double> w;
         SolveResult r;
         {
@@ -1051,7 +1075,8 @@ PYBIND11_MODULE(_native, m) {
         return py::make_tuple(r, wa);
       },
       py::arg("prob"), py::arg("grid"), py::arg("opt") = SolveOptions(), py::arg("return_w") = false,
-      py::arg("rhs") = py::none(), py::arg("w0") = py::none(), py::arg("exact") = py::none());
+      py::arg("rhs") = py::none(), py::arg("w0") = py::none(), py::arg("exact") = py::none(),
+      py::arg("reaction") = py::none());
 
   // The same with fields and / or the result in device memory: rhs_dev /
   // w0_dev / exact_dev = (address of element [0][0], stride_i, stride_j, float32 flag) of
@@ -1063,13 +1088,15 @@ PYBIND11_MODULE(_native, m) {
       "device_solve_group_grid_device",
       [](const Problem& P, const ProcessGrid& pg, const SolveOptions& opt, bool return_w, py::object rhs,
          py::object w0, py::object rhs_dev, py::object w0_dev, py::object w_dev, uintptr_t stream, py::object exact,
-         py::object exact_dev) {
-        FieldArr hr, hw, he;
+         py::object exact_dev, py::object reaction, py::object reaction_dev) {
+        FieldArr hr, hw, he, hc;
         UserFields uf;
         uf.rhs = field_ptr(rhs, P.M - 1, P.N - 1, "rhs", hr);
         uf.w0 = field_ptr(w0, P.M - 1, P.N - 1, "w0", hw);
         uf.exact = field_ptr(exact, P.M - 1, P.N - 1, "exact", he);
+        uf.reaction = field_ptr(reaction, P.M - 1, P.N - 1, "reaction", hc);
         DeviceFields df;
+        device_spec(reaction_dev, df.reaction, df.reaction_si, df.reaction_sj, df.reaction_f32);
         df.stream = reinterpret_cast<hipStream_t>(stream);
         device_spec(rhs_dev, df.rhs, df.rhs_si, df.rhs_sj, df.rhs_f32);
         device_spec(w0_dev, df.w0, df.w0_si, df.w0_sj, df.w0_f32);
@@ -1093,7 +1120,8 @@ PYBIND11_MODULE(_native, m) {
       py::arg("prob"), py::arg("grid"), py::arg("opt") = SolveOptions(), py::arg("return_w") = false,
       py::arg("rhs") = py::none(), py::arg("w0") = py::none(), py::arg("rhs_dev") = py::none(),
       py::arg("w0_dev") = py::none(), py::arg("w_dev") = py::none(), py::arg("stream") = 0,
-      py::arg("exact") = py::none(), py::arg("exact_dev") = py::none());
+      py::arg("exact") = py::none(), py::arg("exact_dev") = py::none(), py::arg("reaction") = py::none(),
+      py::arg("reaction_dev") = py::none());
 
   // The same with the gradient of the solution (pe/fields.hpp): grad = 1 the
   // functionals only (the result's integral / energy / grad_max), 2 the field
@@ -1104,15 +1132,17 @@ PYBIND11_MODULE(_native, m) {
       "device_solve_group_grad",
       [](const Problem& P, const ProcessGrid& pg, const SolveOptions& opt, bool return_w, int grad, py::object rhs,
          py::object w0, py::object exact, py::object rhs_dev, py::object w0_dev, py::object exact_dev, py::object w_dev,
-         py::object grad_dev, uintptr_t stream) {
+         py::object grad_dev, uintptr_t stream, py::object reaction, py::object reaction_dev) {
         if (grad != 1 && grad != 2) throw std::invalid_argument("grad: 1 (functionals) or 2 (field)");
-        FieldArr hr, hw, he;
+        FieldArr hr, hw, he, hc;
         UserFields uf;
+        uf.reaction = field_ptr(reaction, P.M - 1, P.N - 1, "reaction", hc);
         uf.rhs = field_ptr(rhs, P.M - 1, P.N - 1, "rhs", hr);
         uf.w0 = field_ptr(w0, P.M - 1, P.N - 1, "w0", hw);
         uf.exact = field_ptr(exact, P.M - 1, P.N - 1, "exact", he);
         DeviceFields df;
         df.stream = reinterpret_cast<hipStream_t>(stream);
+        device_spec(reaction_dev, df.reaction, df.reaction_si, df.reaction_sj, df.reaction_f32);
         device_spec(rhs_dev, df.rhs, df.rhs_si, df.rhs_sj, df.rhs_f32);
         device_spec(w0_dev, df.w0, df.w0_si, df.w0_sj, df.w0_f32);
         device_spec(exact_dev, df.exact, df.exact_si, df.exact_sj, df.exact_f32);
@@ -1146,7 +1176,8 @@ PYBIND11_MODULE(_native, m) {
       py::arg("prob"), py::arg("grid"), py::arg("opt"), py::arg("return_w"), py::arg("grad"), py::arg("rhs") = py::none(),
       py::arg("w0") = py::none(), py::arg("exact") = py::none(), py::arg("rhs_dev") = py::none(),
       py::arg("w0_dev") = py::none(), py::arg("exact_dev") = py::none(), py::arg("w_dev") = py::none(),
-      py::arg("grad_dev") = py::none(), py::arg("stream") = 0);
+      py::arg("grad_dev") = py::none(), py::arg("stream") = 0, py::arg("reaction") = py::none(),
+      py::arg("reaction_dev") = py::none());
 
   // The operator (residual: B − A w) on P virtual ranks of one device: v / rhs
   // as host arrays or device specs (address, stride_i, stride_j, float32
@@ -1155,9 +1186,12 @@ PYBIND11_MODULE(_native, m) {
   m.def(
       "device_apply_group",
       [](const Problem& P, const ProcessGrid& pg, const SolveOptions& opt, bool residual, py::object v, py::object v_dev,
-         py::object rhs, py::object rhs_dev, py::object out_dev, bool field, uintptr_t stream) {
-        FieldArr hv, hr;
+         py::object rhs, py::object rhs_dev, py::object out_dev, bool field, uintptr_t stream, py::object reaction,
+         py::object reaction_dev) {
+        FieldArr hv, hr, hc;
         OperatorFields f;
+        f.reaction_host = field_ptr(reaction, P.M - 1, P.N - 1, "reaction", hc);
+        device_spec(reaction_dev, f.reaction, f.reaction_si, f.reaction_sj, f.reaction_f32);
         f.v_host = field_ptr(v, P.M - 1, P.N - 1, "field", hv);
         f.rhs_host = field_ptr(rhs, P.M - 1, P.N - 1, "rhs", hr);
         device_spec(v_dev, f.v, f.v_si, f.v_sj, f.v_f32);
@@ -1182,7 +1216,8 @@ PYBIND11_MODULE(_native, m) {
       },
       py::arg("prob"), py::arg("grid"), py::arg("opt"), py::arg("residual") = false, py::arg("v") = py::none(),
       py::arg("v_dev") = py::none(), py::arg("rhs") = py::none(), py::arg("rhs_dev") = py::none(),
-      py::arg("out_dev") = py::none(), py::arg("field") = true, py::arg("stream") = 0);
+      py::arg("out_dev") = py::none(), py::arg("field") = true, py::arg("stream") = 0, py::arg("reaction") = py::none(),
+      py::arg("reaction_dev") = py::none());
 
   // Single-shot device ops for numerics tests: `p` is a full local field
   // (rows × pitch, halo included); returns arrays of the same shape.

@@ -16,6 +16,22 @@ void check_shift(const Problem& P, const char* who) {
                                 "): a negative shift makes the system indefinite");
 }
 
+void check_reaction(const Problem& P, const double* c, const char* who) {
+  if (!P.reaction && !c) return;
+  if (P.reaction != (c != nullptr))
+    throw std::invalid_argument(std::string(who) + ": Problem::reaction and the reaction field go together (the flag is " +
+                                (P.reaction ? "set without a field" : "unset with a field") + ")");
+  if (P.shift != 0.0)
+    throw std::invalid_argument(std::string(who) + ": reaction together with shift != 0 (got " + std::to_string(P.shift) +
+                                "): add the constant to the field");
+  const int64_t n = (int64_t(P.M) - 1) * (int64_t(P.N) - 1);
+  for (int64_t q = 0; q < n; ++q)
+    if (!std::isfinite(c[q]) || c[q] < 0.0)
+      throw std::invalid_argument(std::string(who) + ": reaction must be finite and >= 0 at every node (entry " +
+                                  std::to_string(q) + " is " + std::to_string(c[q]) +
+                                  "): a negative coefficient can make the system indefinite");
+}
+
 void check_stop(const Problem& P, const char* who) {
   if (P.stop != Stop::Step && P.stop != Stop::Residual)
     throw std::invalid_argument(std::string(who) + ": stop must be \"step\" or \"residual\"");
@@ -96,8 +112,8 @@ namespace {
 // coefficient rows a_i, a_{i+1} (vertical faces left of the nodes of rows i,
 // i+1) and b_i (horizontal faces below the nodes of row i, columns 1 .. N)
 // are formed row by row with assemble()'s expressions.
-double operator_rows(const Problem& P, const double* v, bool resid, const double* rhs, double* out, int64_t lo,
-                     int64_t hi) {
+double operator_rows(const Problem& P, const double* v, bool resid, const double* rhs, const double* cr, double* out,
+                     int64_t lo, int64_t hi) {
   const int64_t M = P.M, N = P.N, gny = N - 1;
   const double h1 = P.h1(), h2 = P.h2(), eps = P.eps();
   const bool shifted = P.shift != 0.0;
@@ -126,7 +142,8 @@ double operator_rows(const Problem& P, const double* v, bool resid, const double
       const double c = at(i, j);
       const double Ax = -1.0 / h1 * (a1[size_t(j)] * (at(i + 1, j) - c) / h1 - a0[size_t(j)] * (c - at(i - 1, j)) / h1);
       const double Ay = -1.0 / h2 * (b[size_t(j + 1)] * (at(i, j + 1) - c) / h2 - b[size_t(j)] * (c - at(i, j - 1)) / h2);
-      const double Av = shifted ? shifted_apply(Ax + Ay, P.shift, c) : Ax + Ay;
+      const double Av = cr ? shifted_apply(Ax + Ay, cr[(i - 1) * gny + (j - 1)], c)
+                           : shifted ? shifted_apply(Ax + Ay, P.shift, c) : Ax + Ay;
       double o = Av;
       if (resid) {
         const double y = P.A2 + j * h2;
@@ -140,18 +157,19 @@ double operator_rows(const Problem& P, const double* v, bool resid, const double
   return s;
 }
 
-double operator_pass(const Problem& P, const double* v, bool resid, const double* rhs, double* out, int T,
-                     const char* what) {
+double operator_pass(const Problem& P, const double* v, bool resid, const double* rhs, const double* cr, double* out,
+                     int T, const char* what) {
   if (!v) throw std::invalid_argument(std::string(what) + ": null array");
   if (P.M < 2 || P.N < 2) throw std::invalid_argument(std::string(what) + ": grid too small");
   check_shift(P, what);
+  check_reaction(P, cr, what);
   const int64_t nx = int64_t(P.M) - 1;
-  if (T <= 1) return P.h1() * P.h2() * operator_rows(P, v, resid, rhs, out, 1, nx);
+  if (T <= 1) return P.h1() * P.h2() * operator_rows(P, v, resid, rhs, cr, out, 1, nx);
   // thread t: the contiguous rows 1 + nx t / T .. nx (t + 1) / T; partials added in thread order
   std::vector<double> part(size_t(T), 0.0);
 #pragma omp parallel for schedule(static, 1) num_threads(T)
   for (int t = 0; t < T; ++t)
-    part[size_t(t)] = operator_rows(P, v, resid, rhs, out, 1 + (nx * t) / T, (nx * (t + 1)) / T);
+    part[size_t(t)] = operator_rows(P, v, resid, rhs, cr, out, 1 + (nx * t) / T, (nx * (t + 1)) / T);
   double s = 0.0;
   for (int t = 0; t < T; ++t) s += part[size_t(t)];
   return P.h1() * P.h2() * s;
@@ -159,12 +177,13 @@ double operator_pass(const Problem& P, const double* v, bool resid, const double
 
 }  // namespace
 
-double apply_operator(const Problem& P, const double* v, double* out, int threads) {
-  return operator_pass(P, v, false, nullptr, out, threads, "apply_operator");
+double apply_operator(const Problem& P, const double* v, double* out, int threads, const double* reaction) {
+  return operator_pass(P, v, false, nullptr, reaction, out, threads, "apply_operator");
 }
 
-double residual_field(const Problem& P, const double* w, const double* rhs, double* out, int threads) {
-  return operator_pass(P, w, true, rhs, out, threads, "residual_field");
+double residual_field(const Problem& P, const double* w, const double* rhs, double* out, int threads,
+                      const double* reaction) {
+  return operator_pass(P, w, true, rhs, reaction, out, threads, "residual_field");
 }
 
 }  // namespace pe

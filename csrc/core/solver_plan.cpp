@@ -45,7 +45,16 @@ SolverPlan plan_solver(const Problem& prob, const Block& blk, int comm_size, con
   // do not carry the shift, and nothing below may launch one of them.
   check_shift(prob, "DeviceSolver");
   check_stop(prob, "DeviceSolver");
-  const bool shifted = prob.shift != 0.0;
+  // A reaction field (Problem::reaction) is planned as a shift is: the same
+  // kernels carry it (their FIELD instantiations), and no others.
+  if (prob.reaction && prob.shift != 0.0)
+    throw std::invalid_argument("DeviceSolver: reaction together with shift != 0 (got " + std::to_string(prob.shift) +
+                                "): add the constant to the field");
+  if (prob.reaction && opt.algo >= 2)
+    throw std::invalid_argument(
+        "algo fused / two-step / three-step: the single-sweep kernels implement the operator without a reaction field "
+        "only; a problem with reaction runs algo auto or classic");
+  const bool shifted = prob.shift != 0.0 || prob.reaction;
   if (shifted && opt.algo >= 2)
     throw std::invalid_argument(
         "algo fused / two-step / three-step: the single-sweep kernels implement the unshifted operator only; a problem "

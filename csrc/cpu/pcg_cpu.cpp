@@ -94,9 +94,11 @@ void assemble(const Problem& P, const Block& blk, Fields& f, int T, const double
 }
 
 // Ap = A p on owned nodes (reference mat_A_local :194-213, same expression);
-// shift σ ≠ 0: A_σ p = (Ax + Ay) + σ·p (pe/fields.hpp).
+// shift σ ≠ 0: A_σ p = (Ax + Ay) + σ·p (pe/fields.hpp).  `cr`: the block's
+// owned nx × ny share of a reaction field (null: none) — the same tree with
+// c_ij for σ at every node, zeros included.
 void apply_A(const Block& blk, const double* w, const double* a, const double* b, double* Aw,
-             double h1, double h2, int T, double shift) {
+             double h1, double h2, int T, double shift, const double* cr) {
   const int64_t pitch = blk.pitch;
 #pragma omp parallel for schedule(static) num_threads(T) if (T > 1)
   for (int64_t li = 1; li <= blk.nx; ++li) {
@@ -105,21 +107,24 @@ void apply_A(const Block& blk, const double* w, const double* a, const double* b
       const double Ax = -1.0 / h1 *
                         (a[c + pitch] * (w[c + pitch] - w[c]) / h1 - a[c] * (w[c] - w[c - pitch]) / h1);
       const double Ay = -1.0 / h2 * (b[c + 1] * (w[c + 1] - w[c]) / h2 - b[c] * (w[c] - w[c - 1]) / h2);
-      Aw[c] = shift != 0.0 ? shifted_apply(Ax + Ay, shift, w[c]) : Ax + Ay;
+      if (cr) Aw[c] = shifted_apply(Ax + Ay, cr[(li - 1) * blk.ny + (lj - 1)], w[c]);
+      else Aw[c] = shift != 0.0 ? shifted_apply(Ax + Ay, shift, w[c]) : Ax + Ay;
     }
   }
 }
 
-// z = D^{-1} r (reference mat_D :219-232; D recomputed from a, b); shift σ ≠ 0: D_σ = D + σ.
+// z = D^{-1} r (reference mat_D :219-232; D recomputed from a, b); shift σ ≠ 0: D_σ = D + σ;
+// a reaction field `cr` (owned nx × ny, null: none): D + c_ij.
 void apply_Dinv(const Block& blk, const double* r, const double* a, const double* b, double* z,
-                double h1, double h2, int T, double shift) {
+                double h1, double h2, int T, double shift, const double* cr) {
   const int64_t pitch = blk.pitch;
 #pragma omp parallel for schedule(static) num_threads(T) if (T > 1)
   for (int64_t li = 1; li <= blk.nx; ++li) {
     for (int64_t lj = 1; lj <= blk.ny; ++lj) {
       const int64_t c = blk.at(li, lj);
       double D = (a[c + pitch] + a[c]) / (h1 * h1) + (b[c + 1] + b[c]) / (h2 * h2);
-      if (shift != 0.0) D = shifted_diag(D, shift);
+      if (cr) D = shifted_diag(D, cr[(li - 1) * blk.ny + (lj - 1)]);
+      else if (shift != 0.0) D = shifted_diag(D, shift);
       z[c] = (D != 0.0) ? r[c] / D : 0.0;
     }
   }
@@ -182,6 +187,7 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
                     std::vector<double>* w_out, const UserFields& uf) {
   check_shift(P, "cpu_pcg");
   check_stop(P, "cpu_pcg");
+  check_reaction(P, uf.reaction, "cpu_pcg");
   const auto t_start = clk::now();
   SolveResult res;
   res.backend = opt.threads > 1 ? "cpu-omp" : "cpu-serial";
@@ -199,6 +205,10 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
     assemble(P, blk, f, T, uf.rhs ? rhs.data() : nullptr);
   }
   HaloExchanger halo(blk);
+  // The reaction field at the owned nodes (ring 0: the host path needs no more).
+  std::vector<double> creact;
+  if (uf.reaction) creact = block_field(uf.reaction, P.M, P.N, blk, 0);
+  const double* cr = uf.reaction ? creact.data() : nullptr;
 
   // Initial guess: w⁰ = 0 (reference :384), a deterministic random field, or
   // the user's (its ring travels with the slice: no exchange before r⁰).
@@ -212,7 +222,7 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
         for (int64_t lj = 0; lj <= blk.ny + 1; ++lj)
           f.w[blk.at(li, lj)] = random_w0(blk.i0 - 1 + li, blk.j0 - 1 + lj, P.M, P.N, opt.seed, opt.init_amp);
     }
-    apply_A(blk, f.w.data(), f.a.data(), f.b.data(), f.Ap.data(), h1, h2, T, P.shift);
+    apply_A(blk, f.w.data(), f.a.data(), f.b.data(), f.Ap.data(), h1, h2, T, P.shift, cr);
     for (int64_t li = 1; li <= blk.nx; ++li)
       for (int64_t lj = 1; lj <= blk.ny; ++lj) {
         const int64_t c = blk.at(li, lj);
@@ -222,7 +232,7 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
   } else {
     f.r = f.B;
   }
-  apply_Dinv(blk, f.r.data(), f.a.data(), f.b.data(), f.z.data(), h1, h2, T, P.shift);
+  apply_Dinv(blk, f.r.data(), f.a.data(), f.b.data(), f.z.data(), h1, h2, T, P.shift, cr);
   f.p = f.z;
   // p's halo ring must come from the exchange (reference :392: p = z copies
   // whole matrices, whose halo is 0 before the first exchange).
@@ -258,7 +268,7 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
     auto t1 = clk::now();
     res.t.halo += secs(t0, t1);
 
-    apply_A(blk, f.p.data(), f.a.data(), f.b.data(), f.Ap.data(), h1, h2, T, P.shift);
+    apply_A(blk, f.p.data(), f.a.data(), f.b.data(), f.Ap.data(), h1, h2, T, P.shift, cr);
     auto t2 = clk::now();
     res.t.gpu += secs(t1, t2);
     const double* Ap = f.Ap.data();
@@ -310,7 +320,7 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
     auto t5 = clk::now();
     res.t.gpu += secs(t4, t5);
 
-    apply_Dinv(blk, f.r.data(), f.a.data(), f.b.data(), f.z.data(), h1, h2, T, P.shift);
+    apply_Dinv(blk, f.r.data(), f.a.data(), f.b.data(), f.z.data(), h1, h2, T, P.shift, cr);
     auto t6 = clk::now();
     res.t.prec += secs(t5, t6);
     double zr_new = row_sum(blk, T, [&](int64_t c) { return z[c] * r[c]; }) * h1 * h2;
@@ -365,8 +375,9 @@ SolveResult cpu_pcg(const Problem& P, const Block& blk, HostComm& comm, const So
     }
     comm.allreduce_sum(acc, 1);
     comm.allreduce_max(mx, 2);
-    // (a user right-hand side, or a shifted operator, without a user exact solution has nothing to compare with: -1)
-    const bool no_exact = (uf.rhs || P.shift != 0.0) && !uf.exact;
+    // (a user right-hand side, a shifted operator or a reaction field without a user exact solution has nothing to
+    // compare with: -1)
+    const bool no_exact = (uf.rhs || P.shift != 0.0 || uf.reaction) && !uf.exact;
     res.l2_err = no_exact ? -1.0 : std::sqrt(acc[0] * h1 * h2);
     res.max_err = no_exact ? -1.0 : mx[0];
     res.max_outside = mx[1];
@@ -390,6 +401,7 @@ SolveResult cpu_pcg_threads(const Problem& P, const ProcessGrid& pg, const Solve
                             std::vector<double>* w_out, const UserFields& uf) {
   check_shift(P, "cpu_pcg");  // (before any rank thread starts)
   check_stop(P, "cpu_pcg");
+  check_reaction(P, uf.reaction, "cpu_pcg");
   const int ranks = pg.Px * pg.Py;
   auto group = make_thread_group(ranks);
   std::vector<SolveResult> results(ranks);

@@ -107,7 +107,7 @@ DeviceSolver::DeviceSolver(const Problem& prob, const Block& blk, DeviceComm* co
   cus_ = device_cus(true);
   k.ncu = cus_;
   facts_.cus = cus_;
-  facts_.per_cu = fused_ ? dev::resident_blocks_S(k, 2) : dev::resident_blocks_classic(opt_.variant, prob_.shift != 0.0);
+  facts_.per_cu = fused_ ? dev::resident_blocks_S(k, 2) : dev::resident_blocks_classic(opt_.variant, prob_.shift != 0.0, prob_.reaction);
   facts_.per_cu0 = fused_ ? dev::resident_blocks_S(k, 0) : 0;
   finish_plan(plan_, blk_, facts_);
   nslot_cap_ = plan_.nslot_cap;
@@ -260,6 +260,10 @@ void DeviceSolver::allocate_fields() {
     k.p[0] = fields_ + 2 * A + blk_.base;
     k.p[1] = fields_ + 3 * A + blk_.base;
     hsize_ = std::max<int64_t>(1, nx);
+    if (prob_.reaction) {  // the reaction plane: a p plane's allocation, zero until set_reaction* fills block and ring
+      PE_HIP_CHECK(hipMalloc(&react_dev_, sizeof(double) * A));
+      PE_HIP_CHECK(hipMemsetAsync(react_dev_, 0, sizeof(double) * A, stream_));
+    }
   }
 }
 
@@ -374,6 +378,8 @@ void DeviceSolver::fill_kparams(const EnvKnobs& env) {
   k.dinv_in = 1.0 / ((1.0 + 1.0) * k.ih1sq + (1.0 + 1.0) * k.ih2sq);
   k.dinv_out = 1.0 / ((k.inv_eps + k.inv_eps) * k.ih1sq + (k.inv_eps + k.inv_eps) * k.ih2sq);
   k.stop_res = prob_.stop == Stop::Residual ? 1 : 0;
+  // (a reaction field: the FIELD instantiations; the four diagonal constants stay unshifted, the kernels add c per node)
+  k.creact = react_dev_ ? react_dev_ + blk_.base : nullptr;
   k.shift = prob_.shift;
   if (k.shift != 0.0) {  // the diagonal of A + σI in the two uniform classes (pe/fields.hpp; the band adds σ in cset)
     k.D_in = shifted_diag(k.D_in, k.shift);
@@ -494,6 +500,30 @@ void DeviceSolver::set_rhs(const double* owned) { set_plane(&rhs_dev_, owned, bl
 void DeviceSolver::set_w0(const double* ringed) { set_plane(&w0_dev_, ringed, (blk_.nx + 2) * (blk_.ny + 2)); }
 
 void DeviceSolver::set_exact(const double* owned) { set_plane(&exact_dev_, owned, blk_.nx * blk_.ny); }
+
+// The dense ring plane → the plane the kernels read, in stream order behind the
+// upload / slice and behind every kernel of an earlier solve.
+void DeviceSolver::place_reaction() {
+  dev::launch_ring_to_pitched(react_ring_, blk_.nx, blk_.ny, react_dev_ + blk_.base, blk_.pitch, stream_);
+  PE_HIP_CHECK(hipGetLastError());
+  react_set_ = true;
+}
+
+void DeviceSolver::set_reaction(const double* ringed) {
+  if (!prob_.reaction)
+    throw std::invalid_argument("reaction: this solver was constructed without Problem::reaction (the layout is fixed at construction)");
+  if (!ringed) throw std::invalid_argument("reaction: null field on a solver constructed with Problem::reaction");
+  set_plane(&react_ring_, ringed, (blk_.nx + 2) * (blk_.ny + 2));
+  place_reaction();
+}
+
+void DeviceSolver::set_reaction_device(const void* g, int64_t si, int64_t sj, bool f32, hipStream_t producer) {
+  if (!prob_.reaction)
+    throw std::invalid_argument("reaction: this solver was constructed without Problem::reaction (the layout is fixed at construction)");
+  if (!g) throw std::invalid_argument("reaction: null field on a solver constructed with Problem::reaction");
+  set_plane_device(&react_ring_, 1, g, si, sj, f32, producer, "reaction");
+  place_reaction();
+}
 
 // Device memory of this solver's device at elements [0] and [last] of `p`
 // (hipPointerGetAttributes), and — where the runtime knows the allocation's
@@ -649,6 +679,8 @@ DeviceSolver::~DeviceSolver() {
   if (put_cnt_) (void)hipFree(put_cnt_);
   if (stage_) (void)hipHostFree(stage_);
   if (rhs_dev_) (void)hipFree(rhs_dev_);
+  if (react_ring_) (void)hipFree(react_ring_);
+  if (react_dev_) (void)hipFree(react_dev_);
   if (w0_dev_) (void)hipFree(w0_dev_);
   if (exact_dev_) (void)hipFree(exact_dev_);
   (void)hipFree(partial_);
@@ -1184,6 +1216,8 @@ void DeviceSolver::enqueue_apply(const void* v, int64_t si, int64_t sj, bool f32
 double DeviceSolver::operator_pass(const void* v, int64_t si, int64_t sj, bool f32, bool resid, double* dst, int64_t dsi,
                                    int64_t dsj, int64_t off_i, int64_t off_j, hipStream_t caller) {
   check_apply_span(v, si, sj, f32, dst, dsi, dsj, off_i, off_j);
+  if (prob_.reaction && !react_set_)
+    throw std::invalid_argument("reaction: the problem has a reaction field and none is set (set_reaction / set_reaction_device)");
   io_events();
   PE_HIP_CHECK(hipEventRecord(ev_io_[0], caller));
   PE_HIP_CHECK(hipStreamWaitEvent(stream_, ev_io_[0], 0));
@@ -1246,6 +1280,8 @@ void DeviceSolver::synchronize() {
 }
 
 void DeviceSolver::reset() {
+  if (prob_.reaction && !react_set_)
+    throw std::invalid_argument("reaction: the problem has a reaction field and none is set (set_reaction / set_reaction_device)");
   par_ = 0;
   scratch_used_ = false;
   enqueue_init();
@@ -1537,8 +1573,9 @@ SolveResult DeviceSolver::solve() {
     if (res.converged) res.res_nat = std::sqrt(hs.rz_cur);
   }
   if (opt_.compute_error) {
-    // (a user right-hand side, or a shifted operator, without a user exact solution has nothing to compare with: -1)
-    const bool no_exact = (rhs_dev_ || prob_.shift != 0.0) && !exact_dev_;
+    // (a user right-hand side, a shifted operator or a reaction field without a user exact solution has nothing to
+    // compare with: -1)
+    const bool no_exact = (rhs_dev_ || prob_.shift != 0.0 || prob_.reaction) && !exact_dev_;
     res.l2_err = no_exact ? -1.0 : std::sqrt(hs.err[0] * prob_.h1() * prob_.h2());
     res.max_err = no_exact ? -1.0 : hs.err[1];
     res.max_outside = hs.err[2];
@@ -1661,11 +1698,19 @@ SolveResult device_solve_group(const Problem& P, const ProcessGrid& pg, const So
                                const GroupGradient& gg) {
   const auto t_start = clk::now();
   const int ranks = pg.Px * pg.Py;
+  // the reaction field: a host array is checked here, a device array by its producer (before any launch either way)
+  if (df.reaction) {
+    if (!P.reaction) throw std::invalid_argument("device_solve_group: a reaction field without Problem::reaction");
+  } else {
+    check_reaction(P, uf.reaction, "device_solve_group");
+  }
   std::vector<std::unique_ptr<DeviceSolver>> s;
   std::vector<Block> blks;
   for (int r = 0; r < ranks; ++r) {
     blks.push_back(decompose(P.M, P.N, pg, r));
     s.push_back(std::make_unique<DeviceSolver>(P, blks.back(), nullptr, opt));
+    if (df.reaction) s.back()->set_reaction_device(df.reaction, df.reaction_si, df.reaction_sj, df.reaction_f32, df.stream);
+    else if (uf.reaction) s.back()->set_reaction(block_field(uf.reaction, P.M, P.N, blks.back(), 1).data());
     if (df.rhs) s.back()->set_rhs_device(df.rhs, df.rhs_si, df.rhs_sj, df.rhs_f32, df.stream);
     else if (uf.rhs) s.back()->set_rhs(block_field(uf.rhs, P.M, P.N, blks.back(), 0).data());
     if (df.w0) s.back()->set_w0_device(df.w0, df.w0_si, df.w0_sj, df.w0_f32, df.stream);
@@ -1867,7 +1912,7 @@ SolveResult device_solve_group(const Problem& P, const ProcessGrid& pg, const So
     if (res.converged) res.res_nat = std::sqrt(hs.rz_cur);
   }
   if (opt.compute_error) {
-    const bool no_exact = (uf.rhs || df.rhs || P.shift != 0.0) && !(uf.exact || df.exact);
+    const bool no_exact = (uf.rhs || df.rhs || P.shift != 0.0 || P.reaction) && !(uf.exact || df.exact);
     res.l2_err = no_exact ? -1.0 : std::sqrt(hs.err[0] * P.h1() * P.h2());
     res.max_err = no_exact ? -1.0 : hs.err[1];
     res.max_outside = hs.err[2];
@@ -1904,11 +1949,18 @@ double device_apply_group(const Problem& P, const ProcessGrid& pg, const SolveOp
   if (f.dst && f.host) throw std::invalid_argument("out: a host or a device destination, not both");
   const int ranks = pg.Px * pg.Py;
   const int64_t gny = int64_t(P.N) - 1, gn = (int64_t(P.M) - 1) * gny;
+  if (f.reaction) {
+    if (!P.reaction) throw std::invalid_argument("device_apply_group: a reaction field without Problem::reaction");
+  } else {
+    check_reaction(P, f.reaction_host, "device_apply_group");
+  }
   std::vector<std::unique_ptr<DeviceSolver>> s;
   std::vector<Block> blks;
   for (int r = 0; r < ranks; ++r) {
     blks.push_back(decompose(P.M, P.N, pg, r));
     s.push_back(std::make_unique<DeviceSolver>(P, blks.back(), nullptr, opt));
+    if (f.reaction) s.back()->set_reaction_device(f.reaction, f.reaction_si, f.reaction_sj, f.reaction_f32, f.stream);
+    else if (f.reaction_host) s.back()->set_reaction(block_field(f.reaction_host, P.M, P.N, blks.back(), 1).data());
     if (!residual) continue;
     if (f.rhs) s.back()->set_rhs_device(f.rhs, f.rhs_si, f.rhs_sj, f.rhs_f32, f.stream);
     else if (f.rhs_host) s.back()->set_rhs(block_field(f.rhs_host, P.M, P.N, blks.back(), 0).data());

@@ -61,27 +61,48 @@ __device__ __forceinline__ double coefB(const KParams& k, int64_t q, double half
 // Jacobi diagonal (EXACT: D, used as r / D; fast: 1/D, used as r * dinv).
 // SHIFT (Problem::shift = σ ≠ 0, kernels.hip only): the diagonal of A + σI —
 // the host sets D_in / D_out / dinv_in / dinv_out with σ, the band adds it here.
+// FIELD (Problem::reaction, kernels.hip only): the diagonal of A + diag(c) with
+// the node's own c_ij = `cv` for σ — the same trees at every node, c_ij = 0
+// included.  D_in / D_out / dinv_in / dinv_out stay unshifted; the two uniform
+// classes form shifted_diag(D, cv) per node (fast: 1 / (its own sum of
+// products + cv), the expression the host evaluates for a constant shift).
 struct CS {
   double a0, a1, b0, b1, d;
 };
 
-template <bool EXACT, bool SHIFT = false>
-__device__ __forceinline__ CS cset(const KParams& k, const int* rc, int64_t q, int64_t lj, const TV& t) {
+// The uniform classes' diagonal under FIELD: f = 1 (interior) or 1/eps (exterior).
+template <bool EXACT>
+__device__ __forceinline__ double field_diag(const KParams& k, bool in, double cv) {
+  if constexpr (EXACT) return shifted_diag(in ? k.D_in : k.D_out, cv);
+  else {
+    const double f = in ? 1.0 : k.inv_eps;
+    return 1.0 / shifted_diag((f + f) * k.ih1sq + (f + f) * k.ih2sq, cv);
+  }
+}
+
+template <bool EXACT, bool SHIFT = false, bool FIELD = false>
+__device__ __forceinline__ CS cset(const KParams& k, const int* rc, int64_t q, int64_t lj, const TV& t,
+                                   double cv = 0.0) {
   CS c;
   const int in_lo = cload(rc), in_hi = cload(rc + 1), out_lo = cload(rc + 2), out_hi = cload(rc + 3);
   if (lj >= in_lo && lj <= in_hi) {  // interior: every face fully inside D
     c.a0 = c.a1 = c.b0 = c.b1 = 1.0;
-    c.d = EXACT ? k.D_in : k.dinv_in;
+    if constexpr (FIELD) c.d = field_diag<EXACT>(k, true, cv);
+    else c.d = EXACT ? k.D_in : k.dinv_in;
   } else if (lj < out_lo || lj > out_hi) {  // exterior: every face fully outside D
     c.a0 = c.a1 = c.b0 = c.b1 = k.inv_eps;
-    c.d = EXACT ? k.D_out : k.dinv_out;
+    if constexpr (FIELD) c.d = field_diag<EXACT>(k, false, cv);
+    else c.d = EXACT ? k.D_out : k.dinv_out;
   } else {  // boundary band: evaluate the face lengths
     c.a0 = coefA(k, q, t);
     c.a1 = coefA(k, q + 1, t);
     c.b0 = coefB(k, q, t.hB);
     c.b1 = coefB(k, q, t.hB1);
     // D = (a_{i+1} + a_i)/h1² + (b_{j+1} + b_j)/h2²  (reference mat_D, same order)
-    if constexpr (SHIFT) {
+    if constexpr (FIELD) {
+      if constexpr (EXACT) c.d = shifted_diag((c.a1 + c.a0) / k.h1sq + (c.b1 + c.b0) / k.h2sq, cv);
+      else c.d = 1.0 / shifted_diag((c.a1 + c.a0) * k.ih1sq + (c.b1 + c.b0) * k.ih2sq, cv);
+    } else if constexpr (SHIFT) {
       if constexpr (EXACT) c.d = shifted_diag((c.a1 + c.a0) / k.h1sq + (c.b1 + c.b0) / k.h2sq, k.shift);
       else c.d = 1.0 / shifted_diag((c.a1 + c.a0) * k.ih1sq + (c.b1 + c.b0) * k.ih2sq, k.shift);
     } else if constexpr (EXACT) c.d = (c.a1 + c.a0) / k.h1sq + (c.b1 + c.b0) / k.h2sq;
@@ -89,9 +110,11 @@ __device__ __forceinline__ CS cset(const KParams& k, const int* rc, int64_t q, i
   }
   return c;
 }
-template <bool EXACT, bool SHIFT = false>
+// (FIELD: the node's c from the reaction plane — the p planes' layout, one-node ring included)
+template <bool EXACT, bool SHIFT = false, bool FIELD = false>
 __device__ __forceinline__ CS cset_mem(const KParams& k, int64_t q, int64_t lj) {
-  return cset<EXACT, SHIFT>(k, k.rowcls + (q + 1) * 4, q, lj, tv_at(k, lj));
+  if constexpr (FIELD) return cset<EXACT, SHIFT, true>(k, k.rowcls + (q + 1) * 4, q, lj, tv_at(k, lj), k.creact[q * k.pitch + lj]);
+  else return cset<EXACT, SHIFT>(k, k.rowcls + (q + 1) * 4, q, lj, tv_at(k, lj));
 }
 
 template <bool EXACT>
@@ -101,9 +124,10 @@ __device__ __forceinline__ double zval(const CS& c, double r) {
 }
 
 // SHIFT: A_σ p = A p + σ·p₀ (pe/fields.hpp shifted_apply; kernels.hip only — built without contraction).
-template <bool EXACT, bool SHIFT = false>
+// FIELD: the same with the node's c_ij = `cv` for σ.
+template <bool EXACT, bool SHIFT = false, bool FIELD = false>
 __device__ __forceinline__ double stencil(const KParams& k, const CS& c, double pm, double p0, double pn, double pl,
-                                          double pr) {
+                                          double pr, double cv = 0.0) {
   double Ap;
   if constexpr (EXACT) {
     // Reference apply_A (poisson_mpi_cuda2.cu:526-535), same expression tree.
@@ -113,7 +137,8 @@ __device__ __forceinline__ double stencil(const KParams& k, const CS& c, double 
   } else {
     Ap = (c.a0 * (p0 - pm) - c.a1 * (pn - p0)) * k.ih1sq + (c.b0 * (p0 - pl) - c.b1 * (pr - p0)) * k.ih2sq;
   }
-  if constexpr (SHIFT) return shifted_apply(Ap, k.shift, p0);
+  if constexpr (FIELD) return shifted_apply(Ap, cv, p0);
+  else if constexpr (SHIFT) return shifted_apply(Ap, k.shift, p0);
   else return Ap;
 }
 
@@ -374,9 +399,9 @@ __device__ __forceinline__ void reduce_partials_nm(const double* partial, double
 }
 
 // One p_k value at a single node (strip-edge columns, prologue only).
-template <bool EXACT, bool SHIFT = false>
+template <bool EXACT, bool SHIFT = false, bool FIELD = false>
 __device__ __forceinline__ double p_point(const KParams& k, int64_t q, int64_t lj, double beta, const double* pold) {
-  return zval<EXACT>(cset_mem<EXACT, SHIFT>(k, q, lj), load_r(k, q, lj)) + beta * pold[q * k.pitch + lj];
+  return zval<EXACT>(cset_mem<EXACT, SHIFT, FIELD>(k, q, lj), load_r(k, q, lj)) + beta * pold[q * k.pitch + lj];
 }
 
 // Unconditional 16-byte load (address already clamped in range): a
@@ -399,14 +424,16 @@ __device__ __forceinline__ bool has_gen(const RowCls& c, int64_t jlo, int64_t jh
   if (c.in_lo > c.in_hi) return true;
   return lo < c.in_lo || hi > c.in_hi;
 }
-// Coefficients of a node in a row without boundary-band nodes in this strip.
-template <bool EXACT>
-__device__ __forceinline__ CS cset_fast(const KParams& k, const RowCls& c, int64_t lj) {
+// Coefficients of a node in a row without boundary-band nodes in this strip
+// (FIELD: no constant diagonal — the class's D with the node's c, cset's expression).
+template <bool EXACT, bool FIELD = false>
+__device__ __forceinline__ CS cset_fast(const KParams& k, const RowCls& c, int64_t lj, double cv = 0.0) {
   const bool in = lj >= c.in_lo && lj <= c.in_hi;
   const double f = in ? 1.0 : k.inv_eps;
   CS cs;
   cs.a0 = cs.a1 = cs.b0 = cs.b1 = f;
-  cs.d = EXACT ? (in ? k.D_in : k.D_out) : (in ? k.dinv_in : k.dinv_out);
+  if constexpr (FIELD) cs.d = field_diag<EXACT>(k, in, cv);
+  else cs.d = EXACT ? (in ? k.D_in : k.D_out) : (in ? k.dinv_in : k.dinv_out);
   return cs;
 }
 

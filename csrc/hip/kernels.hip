@@ -52,7 +52,12 @@ struct SegData {
 // F: p_k = D⁻¹ r_k + β p_{k-1} on owned nodes and the halo ring, then
 //    S_den = Σ (A p_k)·p_k and S_pp = Σ p_k·p_k over owned nodes.
 // ---------------------------------------------------------------------------
-template <bool EXACT, bool SHIFT = false>
+// FIELD (Problem::reaction): the row's lane pair of the reaction plane rides
+// with its r / p loads (the same pitch and column origin: one aligned 16-byte
+// load, issued with them) and rotates through registers as p does; the ring
+// column ny+1 sits in the plane itself, the strip-edge nodes read theirs in
+// p_point.
+template <bool EXACT, bool SHIFT = false, bool FIELD = false>
 __global__ __launch_bounds__(TJ) void kF(KParams k, int par) {
   DevState* st = k.st;
   if (st->done) return;
@@ -109,11 +114,11 @@ __global__ __launch_bounds__(TJ) void kF(KParams k, int par) {
         const int q = s0 + t;
         const int jl = j0 - 1, jr = j0 + SW;
         if (valid_node(k, q, jl)) {
-          d.hL = p_point<EXACT, SHIFT>(k, q, jl, beta, pold);
+          d.hL = p_point<EXACT, SHIFT, FIELD>(k, q, jl, beta, pold);
           if (jl == 0) pnew[q * pitch] = d.hL;  // rank-halo column: ours to write
         }
         if (jr <= ny + 1 && valid_node(k, q, jr)) {
-          d.hR = p_point<EXACT, SHIFT>(k, q, jr, beta, pold);
+          d.hR = p_point<EXACT, SHIFT, FIELD>(k, q, jr, beta, pold);
           if (jr == ny + 1) pnew[q * pitch + jr] = d.hR;
         }
       }
@@ -122,19 +127,20 @@ __global__ __launch_bounds__(TJ) void kF(KParams k, int par) {
     };
 
     // p(q) for both elements from r(q), p_{k-1}(q); rh = r of the halo column.
-    auto prow = [&](int q, const RowCls& rc, bool fast, double2 rr, double2 po, double rh, double& v0, double& v1) {
+    auto prow = [&](int q, const RowCls& rc, bool fast, double2 rr, double2 po, double2 cc, double rh, double& v0,
+                    double& v1) {
       const bool rin = q >= 1 && q <= nx;
       const bool rv = rin || (q == 0 && k.has[LEFT]) || (q == nx + 1 && k.has[RIGHT]);
       const double r0 = (c0 == ny + 1) ? rh : rr.x;
       const double r1 = (c1 == ny + 1) ? rh : rr.y;
       CS s0, s1;
       if (fast) {
-        s0 = cset_fast<EXACT>(k, rc, c0);
-        s1 = cset_fast<EXACT>(k, rc, c1);
+        s0 = cset_fast<EXACT, FIELD>(k, rc, c0, cc.x);
+        s1 = cset_fast<EXACT, FIELD>(k, rc, c1, cc.y);
       } else {
         const int* rcp = k.rowcls + (q + 1) * 4;
-        s0 = cset<EXACT, SHIFT>(k, rcp, q, c0, tv_at(k, ca));
-        s1 = cset<EXACT, SHIFT>(k, rcp, q, c1, tv_at(k, ca + 1));
+        s0 = cset<EXACT, SHIFT, FIELD>(k, rcp, q, c0, tv_at(k, ca), cc.x);
+        s1 = cset<EXACT, SHIFT, FIELD>(k, rcp, q, c1, tv_at(k, ca + 1), cc.y);
       }
       const bool e0 = rv && (rin ? live0 : own0), e1 = rv && (rin ? live1 : own1);
       v0 = e0 ? zval<EXACT>(s0, r0) + beta * po.x : 0.0;
@@ -155,6 +161,17 @@ __global__ __launch_bounds__(TJ) void kF(KParams k, int par) {
     double2 rN = ld2(rptr + 2 * pitch), pN = ld2(pptr + 2 * pitch);  // row ib+1
     rptr += 3 * pitch;                                                // → row ib+2
     pptr += 3 * pitch;
+    // (FIELD) c of rows ib-1, ib, ib+1; cI: the stencil row's, cN: the next p row's
+    const double2 cz = make_double2(0.0, 0.0);
+    const double* cptr = nullptr;
+    double2 cA = cz, cI = cz, cN = cz;
+    if constexpr (FIELD) {
+      cptr = k.creact + (ib - 1) * pitch + ca;
+      cA = ld2(cptr);
+      cI = ld2(cptr + pitch);
+      cN = ld2(cptr + 2 * pitch);
+      cptr += 3 * pitch;
+    }
     SegData sd = seg_load(ib, min(ib + SEG - 1, ie));
 
     double pm0, pm1, p00, p01;
@@ -163,8 +180,8 @@ __global__ __launch_bounds__(TJ) void kF(KParams k, int par) {
     {
       const RowCls cm = rcl_read(sd.rcv, 0);  // row ib-1
       const double rupA = (k.has[UP] && ib >= 2) ? k.recv_up[ib - 2] : 0.0;
-      prow(ib - 1, cm, !has_gen(cm, j0, jhi), rA, pA, rupA, pm0, pm1);
-      prow(ib, ci, !gi, rB, pB, readlane(sd.rup, 0), p00, p01);
+      prow(ib - 1, cm, !has_gen(cm, j0, jhi), rA, pA, cA, rupA, pm0, pm1);
+      prow(ib, ci, !gi, rB, pB, cI, readlane(sd.rup, 0), p00, p01);
     }
     if (ib == 1 && k.has[LEFT]) store_row(0, pm0, pm1);
     store_row(ib, p00, p01);
@@ -176,6 +193,11 @@ __global__ __launch_bounds__(TJ) void kF(KParams k, int par) {
       for (int i = s0; i <= s1; ++i) {
         const int q = i + 1;
         const double2 rNN = ld2(rptr), pNN = ld2(pptr);  // row i+2 (≤ nx+3: padded)
+        double2 cNN = cz;
+        if constexpr (FIELD) {
+          cNN = ld2(cptr);
+          cptr += pitch;
+        }
         rptr += pitch;
         pptr += pitch;
 
@@ -184,7 +206,7 @@ __global__ __launch_bounds__(TJ) void kF(KParams k, int par) {
         const bool gq = has_gen(cq, j0, jhi);
         const double rh = readlane(sd.rup, rl + 1);
         double pn0, pn1;
-        prow(q, cq, !gq, rN, pN, rh, pn0, pn1);
+        prow(q, cq, !gq, rN, pN, cN, rh, pn0, pn1);
         if (q <= ie || (q == nx + 1 && k.has[RIGHT])) store_row(q, pn0, pn1);
 
         // j±1 neighbours of row i: DPP wave shifts, strip edges from hL/hR.
@@ -195,15 +217,15 @@ __global__ __launch_bounds__(TJ) void kF(KParams k, int par) {
         if (lane == 63) pr1 = eR;
         CS x0, x1;
         if (!gi) {
-          x0 = cset_fast<EXACT>(k, ci, c0);
-          x1 = cset_fast<EXACT>(k, ci, c1);
+          x0 = cset_fast<EXACT, FIELD>(k, ci, c0, cI.x);
+          x1 = cset_fast<EXACT, FIELD>(k, ci, c1, cI.y);
         } else {
           const int* rcp = k.rowcls + (i + 1) * 4;
-          x0 = cset<EXACT, SHIFT>(k, rcp, i, c0, tv_at(k, ca));
-          x1 = cset<EXACT, SHIFT>(k, rcp, i, c1, tv_at(k, ca + 1));
+          x0 = cset<EXACT, SHIFT, FIELD>(k, rcp, i, c0, tv_at(k, ca), cI.x);
+          x1 = cset<EXACT, SHIFT, FIELD>(k, rcp, i, c1, tv_at(k, ca + 1), cI.y);
         }
-        const double Ap0 = stencil<EXACT, SHIFT>(k, x0, pm0, p00, pn0, pl0, p01);
-        const double Ap1 = stencil<EXACT, SHIFT>(k, x1, pm1, p01, pn1, p00, pr1);
+        const double Ap0 = stencil<EXACT, SHIFT, FIELD>(k, x0, pm0, p00, pn0, pl0, p01, cI.x);
+        const double Ap1 = stencil<EXACT, SHIFT, FIELD>(k, x1, pm1, p01, pn1, p00, pr1, cI.y);
         if (own0) {
           sden += Ap0 * p00;
           spp += p00 * p00;
@@ -218,6 +240,10 @@ __global__ __launch_bounds__(TJ) void kF(KParams k, int par) {
         p01 = pn1;
         rN = rNN;
         pN = pNN;
+        if constexpr (FIELD) {
+          cI = cN;
+          cN = cNN;
+        }
         ci = cq;
         gi = gq;
       }
@@ -246,7 +272,8 @@ __global__ __launch_bounds__(TJ) void kF(KParams k, int par) {
 // ---------------------------------------------------------------------------
 // G: α = rz/den, stop test, w += α p, r -= α A p, S_zr = Σ (D⁻¹r)·r.
 // ---------------------------------------------------------------------------
-template <bool EXACT, bool SHIFT = false>
+// FIELD: the row's c pair rides with its r / w loads (kF's note).
+template <bool EXACT, bool SHIFT = false, bool FIELD = false>
 __global__ __launch_bounds__(TJ) void kG(KParams k, int par) {
   DevState* st = k.st;
   if (st->done) return;
@@ -314,6 +341,14 @@ __global__ __launch_bounds__(TJ) void kG(KParams k, int par) {
     pptr += 3 * pitch;  // → row ib+2
     rptr += pitch;      // → row ib+1
     wptr += pitch;
+    const double2 cz = make_double2(0.0, 0.0);
+    const double* cptr = nullptr;
+    double2 cC = cz;  // (FIELD) c of row i
+    if constexpr (FIELD) {
+      cptr = k.creact + ib * pitch + ca;
+      cC = ld2(cptr);
+      cptr += pitch;
+    }
     double pm0 = pA.x, pm1 = pA.y;
     SegData sd;
 
@@ -324,6 +359,11 @@ __global__ __launch_bounds__(TJ) void kG(KParams k, int par) {
         const double2 pNN = ld2(pptr);  // row i+2 (padded)
         const double2 rNx = ld2(rptr);  // row i+1
         const double2 wNx = ld2(wptr);
+        double2 cNx = cz;
+        if constexpr (FIELD) {
+          cNx = ld2(cptr);  // row i+1 (padded)
+          cptr += pitch;
+        }
         pptr += pitch;
         rptr += pitch;
         wptr += pitch;
@@ -337,15 +377,15 @@ __global__ __launch_bounds__(TJ) void kG(KParams k, int par) {
         if (lane == 63) pr1 = eR;
         CS x0, x1;
         if (!has_gen(ci, j0, jhi)) {
-          x0 = cset_fast<EXACT>(k, ci, c0);
-          x1 = cset_fast<EXACT>(k, ci, c1);
+          x0 = cset_fast<EXACT, FIELD>(k, ci, c0, cC.x);
+          x1 = cset_fast<EXACT, FIELD>(k, ci, c1, cC.y);
         } else {
           const int* rcp = k.rowcls + (i + 1) * 4;
-          x0 = cset<EXACT, SHIFT>(k, rcp, i, c0, tv_at(k, ca));
-          x1 = cset<EXACT, SHIFT>(k, rcp, i, c1, tv_at(k, ca + 1));
+          x0 = cset<EXACT, SHIFT, FIELD>(k, rcp, i, c0, tv_at(k, ca), cC.x);
+          x1 = cset<EXACT, SHIFT, FIELD>(k, rcp, i, c1, tv_at(k, ca + 1), cC.y);
         }
-        const double Ap0 = stencil<EXACT, SHIFT>(k, x0, pm0, pB.x, pN.x, pl0, pB.y);
-        const double Ap1 = stencil<EXACT, SHIFT>(k, x1, pm1, pB.y, pN.y, pB.x, pr1);
+        const double Ap0 = stencil<EXACT, SHIFT, FIELD>(k, x0, pm0, pB.x, pN.x, pl0, pB.y, cC.x);
+        const double Ap1 = stencil<EXACT, SHIFT, FIELD>(k, x1, pm1, pB.y, pN.y, pB.x, pr1, cC.y);
         const double wn0 = wC.x + alpha * pB.x, wn1 = wC.y + alpha * pB.y;
         const double rn0 = rC.x - alpha * Ap0, rn1 = rC.y - alpha * Ap1;
         if (own0) szr += zval<EXACT>(x0, rn0) * rn0;
@@ -370,6 +410,7 @@ __global__ __launch_bounds__(TJ) void kG(KParams k, int par) {
         pN = pNN;
         rC = rNx;
         wC = wNx;
+        if constexpr (FIELD) cC = cNx;
       }
     }
   }
@@ -402,7 +443,7 @@ __global__ __launch_bounds__(TJ) void kG(KParams k, int par) {
 // ---------------------------------------------------------------------------
 // Init: r⁰ = B - A w⁰ (w⁰ = 0 or a global-index hash), S_zr⁰ = Σ (D⁻¹r⁰)·r⁰.
 // ---------------------------------------------------------------------------
-template <bool EXACT, bool SHIFT = false>
+template <bool EXACT, bool SHIFT = false, bool FIELD = false>
 __global__ __launch_bounds__(TJ) void kInit(KParams k, int init_random, unsigned long long seed, double amp) {
   __shared__ double sm[8];
   __shared__ int sflag;
@@ -413,15 +454,17 @@ __global__ __launch_bounds__(TJ) void kInit(KParams k, int init_random, unsigned
     const int64_t li = idx / k.ny + 1, lj = idx % k.ny + 1;
     const int64_t gi = k.gi0 + li, gj = k.gj0 + lj;
     const double x = k.A1 + gi * k.h1, y = k.A2 + gj * k.h2;
-    const CS c = cset_mem<EXACT, SHIFT>(k, li, lj);
+    const CS c = cset_mem<EXACT, SHIFT, FIELD>(k, li, lj);
     double rr = in_ellipse(x, y, k.cx, k.cy) ? k.F : 0.0;
     const int64_t at = li * k.pitch + lj;
+    double cv = 0.0;
+    if constexpr (FIELD) cv = k.creact[at];
     if (init_random) {
       const double w0 = random_w0(gi, gj, k.M, k.N, seed, amp);
-      const double Aw = stencil<EXACT, SHIFT>(k, c, random_w0(gi - 1, gj, k.M, k.N, seed, amp), w0,
+      const double Aw = stencil<EXACT, SHIFT, FIELD>(k, c, random_w0(gi - 1, gj, k.M, k.N, seed, amp), w0,
                                        random_w0(gi + 1, gj, k.M, k.N, seed, amp),
                                        random_w0(gi, gj - 1, k.M, k.N, seed, amp),
-                                       random_w0(gi, gj + 1, k.M, k.N, seed, amp));
+                                       random_w0(gi, gj + 1, k.M, k.N, seed, amp), cv);
       rr = rr - Aw;
       k.w[li * k.wpitch + lj] = w0;
     }
@@ -455,7 +498,7 @@ __global__ __launch_bounds__(TJ) void kInit(KParams k, int init_random, unsigned
 // 0 on the box boundary; null: kInit's zero / hash start).  Same stores (w
 // with wpitch, r with pitch into the live layout — k.r is the classic r or
 // the r-plane of x[0] behind its xorg), same sum protocol.
-template <bool EXACT, bool SHIFT = false>
+template <bool EXACT, bool SHIFT = false, bool FIELD = false>
 __global__ __launch_bounds__(TJ) void kInitField(KParams k, const double* __restrict__ Bp,
                                                  const double* __restrict__ W0, int init_random,
                                                  unsigned long long seed, double amp) {
@@ -468,21 +511,23 @@ __global__ __launch_bounds__(TJ) void kInitField(KParams k, const double* __rest
     const int64_t li = idx / k.ny + 1, lj = idx % k.ny + 1;
     const int64_t gi = k.gi0 + li, gj = k.gj0 + lj;
     const double x = k.A1 + gi * k.h1, y = k.A2 + gj * k.h2;
-    const CS c = cset_mem<EXACT, SHIFT>(k, li, lj);
+    const CS c = cset_mem<EXACT, SHIFT, FIELD>(k, li, lj);
     double rr = in_ellipse(x, y, k.cx, k.cy) ? (Bp ? Bp[idx] : k.F) : 0.0;
     const int64_t at = li * k.pitch + lj;
+    double cv = 0.0;
+    if constexpr (FIELD) cv = k.creact[at];
     if (W0) {
       const int64_t q = li * wc + lj;
       const double w0 = W0[q];
-      const double Aw = stencil<EXACT, SHIFT>(k, c, W0[q - wc], w0, W0[q + wc], W0[q - 1], W0[q + 1]);
+      const double Aw = stencil<EXACT, SHIFT, FIELD>(k, c, W0[q - wc], w0, W0[q + wc], W0[q - 1], W0[q + 1], cv);
       rr = rr - Aw;
       k.w[li * k.wpitch + lj] = w0;
     } else if (init_random) {
       const double w0 = random_w0(gi, gj, k.M, k.N, seed, amp);
-      const double Aw = stencil<EXACT, SHIFT>(k, c, random_w0(gi - 1, gj, k.M, k.N, seed, amp), w0,
+      const double Aw = stencil<EXACT, SHIFT, FIELD>(k, c, random_w0(gi - 1, gj, k.M, k.N, seed, amp), w0,
                                        random_w0(gi + 1, gj, k.M, k.N, seed, amp),
                                        random_w0(gi, gj - 1, k.M, k.N, seed, amp),
-                                       random_w0(gi, gj + 1, k.M, k.N, seed, amp));
+                                       random_w0(gi, gj + 1, k.M, k.N, seed, amp), cv);
       rr = rr - Aw;
       k.w[li * k.wpitch + lj] = w0;
     }
@@ -529,6 +574,19 @@ __global__ __launch_bounds__(256) void kSliceField(const T* __restrict__ g, int6
     double v = 0.0;
     if (gi >= 1 && gi <= gnx && gj >= 1 && gj <= gny) v = double(g[(gi - 1) * si + (gj - 1) * sj]);
     out[idx] = v;
+  }
+}
+
+// A dense (nx+2) × (ny+2) ring plane (kSliceField<T, 1>'s output, or
+// pe::block_field(…, ring = 1) uploaded) into the classic p planes' layout:
+// local (li, lj) at dst + li·pitch + lj (DeviceSolver::set_reaction*: the
+// reaction plane the FIELD kernels load next to p).  Padding stays as allocated (0).
+__global__ __launch_bounds__(256) void kRingToPitched(const double* __restrict__ src, int64_t rows, int64_t cols,
+                                                      double* __restrict__ dst, int64_t pitch) {
+  const int64_t n = rows * cols;
+  for (int64_t idx = int64_t(blockIdx.x) * 256 + threadIdx.x; idx < n; idx += int64_t(gridDim.x) * 256) {
+    const int64_t a = idx / cols, b = idx - a * cols;
+    dst[a * pitch + b] = src[idx];
   }
 }
 
@@ -835,7 +893,8 @@ __device__ __forceinline__ double field_in_row(const T* col, int64_t si, int64_t
   const double v = double(col[(gi - 1) * si]);
   return col_ok ? v : 0.0;
 }
-template <typename T, bool RESID, bool STORE, bool SHIFT = false>
+// FIELD: c of the batch's rows from the reaction plane, loaded with the batch.
+template <typename T, bool RESID, bool STORE, bool SHIFT = false, bool FIELD = false>
 __global__ __launch_bounds__(TJ) void kApplyField(KParams k, const T* __restrict__ g, int64_t si, int64_t sj,
                                                   const double* __restrict__ Bp, int trows, int64_t ctiles,
                                                   int64_t ntiles, double* __restrict__ dst, int64_t dsi, int64_t dsj,
@@ -869,7 +928,7 @@ __global__ __launch_bounds__(TJ) void kApplyField(KParams k, const T* __restrict
     for (int64_t li = li0; li <= li1; li += kApplyU) {
       // a batch of kApplyU rows of loads, all issued before the first row is computed: the row below (dn), the
       // left / right neighbours (dl, dr), the rhs value (db).  Rows past the tile: clamped, loaded, unused.
-      double dn[kApplyU], dl[kApplyU], dr[kApplyU], db[RESID ? kApplyU : 1];
+      double dn[kApplyU], dl[kApplyU], dr[kApplyU], db[RESID ? kApplyU : 1], dc[FIELD ? kApplyU : 1] = {};
 #pragma unroll
       for (int u = 0; u < kApplyU; ++u) {
         const int64_t r = min(li + u, li1), gi = k.gi0 + r;
@@ -877,13 +936,15 @@ __global__ __launch_bounds__(TJ) void kApplyField(KParams k, const T* __restrict
         dl[u] = field_in_row(pl, si, gi, jm_ok);
         dr[u] = field_in_row(pr, si, gi, jp_ok);
         if constexpr (RESID) db[u] = brow[(r - li0) * bstep];
+        if constexpr (FIELD) dc[u] = k.creact[r * k.pitch + lj];
       }
 #pragma unroll
       for (int u = 0; u < kApplyU; ++u) {
         const int64_t q = li + u;
         if (q <= li1) {
-          const CS c = cset<true, SHIFT>(k, k.rowcls + (q + 1) * 4, q, lj, tv);
-          const double Av = stencil<true, SHIFT>(k, c, wm, wc, dn[u], dl[u], dr[u]);
+          const double cv = FIELD ? dc[u] : 0.0;
+          const CS c = cset<true, SHIFT, FIELD>(k, k.rowcls + (q + 1) * 4, q, lj, tv, cv);
+          const double Av = stencil<true, SHIFT, FIELD>(k, c, wm, wc, dn[u], dl[u], dr[u], cv);
           double o = Av;
           if constexpr (RESID) {
             const double x = k.A1 + (k.gi0 + q) * k.h1;
@@ -960,26 +1021,28 @@ __global__ void kGroupReduce(double* const* bufs, int nranks, int n, int is_max)
 }
 
 // Test op: Ap = A p on owned nodes (p halo must be valid).
-template <bool EXACT, bool SHIFT = false>
+template <bool EXACT, bool SHIFT = false, bool FIELD = false>
 __global__ void kApplyA(KParams k, const double* p, double* Ap) {
   const int64_t n = k.nx * k.ny;
   for (int64_t idx = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; idx < n;
        idx += int64_t(gridDim.x) * blockDim.x) {
     const int64_t li = idx / k.ny + 1, lj = idx % k.ny + 1;
     const int64_t c = li * k.pitch + lj;
-    const CS cs = cset_mem<EXACT, SHIFT>(k, li, lj);
-    Ap[c] = stencil<EXACT, SHIFT>(k, cs, p[c - k.pitch], p[c], p[c + k.pitch], p[c - 1], p[c + 1]);
+    const CS cs = cset_mem<EXACT, SHIFT, FIELD>(k, li, lj);
+    double cv = 0.0;
+    if constexpr (FIELD) cv = k.creact[c];
+    Ap[c] = stencil<EXACT, SHIFT, FIELD>(k, cs, p[c - k.pitch], p[c], p[c + k.pitch], p[c - 1], p[c + 1], cv);
   }
 }
 
 // Test op: a_ij, b_ij, D_ij through the class table (checks the classification).
-template <bool SHIFT = false>
+template <bool SHIFT = false, bool FIELD = false>
 __global__ void kCoef(KParams k, double* a, double* b, double* D) {
   const int64_t n = (k.nx + 2) * (k.ny + 2);
   for (int64_t idx = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; idx < n;
        idx += int64_t(gridDim.x) * blockDim.x) {
     const int64_t li = idx / (k.ny + 2), lj = idx % (k.ny + 2);
-    const CS cs = cset_mem<true, SHIFT>(k, li, lj);
+    const CS cs = cset_mem<true, SHIFT, FIELD>(k, li, lj);
     const int64_t c = li * k.pitch + lj;
     a[c] = cs.a0;
     b[c] = cs.b0;
@@ -1003,9 +1066,15 @@ void launch_delay(double us, hipStream_t s) {
   hipLaunchKernelGGL(kDelay, dim3(1), dim3(64), 0, s, ticks);
 }
 
-int resident_blocks_classic(int variant, bool shift) {
+int resident_blocks_classic(int variant, bool shift, bool field) {
   int n = 0, m = 0;
-  if (shift && variant == 1) {
+  if (field && variant == 1) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kF<true, false, true>, TJ, 0) != hipSuccess) n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&m, kG<true, false, true>, TJ, 0) != hipSuccess) m = 0;
+  } else if (field) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kF<false, false, true>, TJ, 0) != hipSuccess) n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&m, kG<false, false, true>, TJ, 0) != hipSuccess) m = 0;
+  } else if (shift && variant == 1) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kF<true, true>, TJ, 0) != hipSuccess) n = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&m, kG<true, true>, TJ, 0) != hipSuccess) m = 0;
   } else if (shift) {
@@ -1031,9 +1100,16 @@ static unsigned flat_blocks(const KParams& k) {
 
 // Problem::shift ≠ 0 → the SHIFT instantiations; each wrapper decides here, once.
 static bool shifted(const KParams& k) { return k.shift != 0.0; }
+// Problem::reaction (the plane is set) → the FIELD instantiations, decided in the same places.
+static bool fielded(const KParams& k) { return k.creact != nullptr; }
 
 void launch_init(const KParams& k, int init_random, unsigned long long seed, double amp, int variant,
                  hipStream_t s) {
+  if (fielded(k)) {
+    if (variant == 1) hipLaunchKernelGGL((kInit<true, false, true>), dim3(flat_blocks(k)), dim3(TJ), 0, s, k, init_random, seed, amp);
+    else hipLaunchKernelGGL((kInit<false, false, true>), dim3(flat_blocks(k)), dim3(TJ), 0, s, k, init_random, seed, amp);
+    return;
+  }
   if (shifted(k)) {
     if (variant == 1) hipLaunchKernelGGL((kInit<true, true>), dim3(flat_blocks(k)), dim3(TJ), 0, s, k, init_random, seed, amp);
     else hipLaunchKernelGGL((kInit<false, true>), dim3(flat_blocks(k)), dim3(TJ), 0, s, k, init_random, seed, amp);
@@ -1045,6 +1121,13 @@ void launch_init(const KParams& k, int init_random, unsigned long long seed, dou
 
 void launch_init_field(const KParams& k, const double* rhs, const double* w0, int init_random,
                        unsigned long long seed, double amp, int variant, hipStream_t s) {
+  if (fielded(k)) {
+    if (variant == 1)
+      hipLaunchKernelGGL((kInitField<true, false, true>), dim3(flat_blocks(k)), dim3(TJ), 0, s, k, rhs, w0, init_random, seed, amp);
+    else
+      hipLaunchKernelGGL((kInitField<false, false, true>), dim3(flat_blocks(k)), dim3(TJ), 0, s, k, rhs, w0, init_random, seed, amp);
+    return;
+  }
   if (shifted(k)) {
     if (variant == 1)
       hipLaunchKernelGGL((kInitField<true, true>), dim3(flat_blocks(k)), dim3(TJ), 0, s, k, rhs, w0, init_random, seed, amp);
@@ -1059,6 +1142,11 @@ void launch_init_field(const KParams& k, const double* rhs, const double* w0, in
 }
 
 void launch_F(const KParams& k, int par, int variant, hipStream_t s) {
+  if (fielded(k)) {
+    if (variant == 1) hipLaunchKernelGGL((kF<true, false, true>), dim3(k.nblocks), dim3(TJ), 0, s, k, par);
+    else hipLaunchKernelGGL((kF<false, false, true>), dim3(k.nblocks), dim3(TJ), 0, s, k, par);
+    return;
+  }
   if (shifted(k)) {
     if (variant == 1) hipLaunchKernelGGL((kF<true, true>), dim3(k.nblocks), dim3(TJ), 0, s, k, par);
     else hipLaunchKernelGGL((kF<false, true>), dim3(k.nblocks), dim3(TJ), 0, s, k, par);
@@ -1069,6 +1157,11 @@ void launch_F(const KParams& k, int par, int variant, hipStream_t s) {
 }
 
 void launch_G(const KParams& k, int par, int variant, hipStream_t s) {
+  if (fielded(k)) {
+    if (variant == 1) hipLaunchKernelGGL((kG<true, false, true>), dim3(k.nblocks), dim3(TJ), 0, s, k, par);
+    else hipLaunchKernelGGL((kG<false, false, true>), dim3(k.nblocks), dim3(TJ), 0, s, k, par);
+    return;
+  }
   if (shifted(k)) {
     if (variant == 1) hipLaunchKernelGGL((kG<true, true>), dim3(k.nblocks), dim3(TJ), 0, s, k, par);
     else hipLaunchKernelGGL((kG<false, true>), dim3(k.nblocks), dim3(TJ), 0, s, k, par);
@@ -1109,6 +1202,11 @@ void launch_slice_field(const void* g, bool f32, int64_t si, int64_t sj, int64_t
   else if (f32) hipLaunchKernelGGL((kSliceField<float, 0>), grid, block, 0, s, gf, si, sj, gnx, gny, i0, j0, rows, cols, out);
   else if (ring) hipLaunchKernelGGL((kSliceField<double, 1>), grid, block, 0, s, gd, si, sj, gnx, gny, i0, j0, rows, cols, out);
   else hipLaunchKernelGGL((kSliceField<double, 0>), grid, block, 0, s, gd, si, sj, gnx, gny, i0, j0, rows, cols, out);
+}
+
+void launch_ring_to_pitched(const double* ring, int64_t nx, int64_t ny, double* dst, int64_t pitch, hipStream_t s) {
+  const int64_t rows = nx + 2, cols = ny + 2;
+  hipLaunchKernelGGL(kRingToPitched, dim3(copy_blocks(rows * cols)), dim3(256), 0, s, ring, rows, cols, dst, pitch);
 }
 
 void launch_gather_w(const KParams& k, double* dst, int64_t si, int64_t sj, int64_t off_i, int64_t off_j,
@@ -1157,7 +1255,7 @@ void launch_grad_field(const KParams& k, const double* plane, int64_t pitch, dou
                        int64_t(0));
 }
 namespace {
-template <typename T, bool RESID, bool SHIFT>
+template <typename T, bool RESID, bool SHIFT, bool FIELD = false>
 void apply_field_launch(const KParams& k, const T* g, int64_t si, int64_t sj, const double* rhs, double* dst,
                         int64_t dsi, int64_t dsj, int64_t off_i, int64_t off_j, hipStream_t s) {
   // launch_grad_field's tiling: ≈ 2048 tiles where the block has them, 8 .. 64 rows each, ≤ 4096 blocks
@@ -1167,10 +1265,10 @@ void apply_field_launch(const KParams& k, const T* g, int64_t si, int64_t sj, co
   const int64_t ntiles = ctiles * ((k.nx + trows - 1) / trows);
   const dim3 grid(unsigned(std::min<int64_t>(ntiles, 4096))), block(TJ);
   if (dst)
-    hipLaunchKernelGGL((kApplyField<T, RESID, true, SHIFT>), grid, block, 0, s, k, g, si, sj, rhs, trows, ctiles, ntiles, dst,
+    hipLaunchKernelGGL((kApplyField<T, RESID, true, SHIFT, FIELD>), grid, block, 0, s, k, g, si, sj, rhs, trows, ctiles, ntiles, dst,
                        dsi, dsj, off_i, off_j);
   else
-    hipLaunchKernelGGL((kApplyField<T, RESID, false, SHIFT>), grid, block, 0, s, k, g, si, sj, rhs, trows, ctiles, ntiles,
+    hipLaunchKernelGGL((kApplyField<T, RESID, false, SHIFT, FIELD>), grid, block, 0, s, k, g, si, sj, rhs, trows, ctiles, ntiles,
                        static_cast<double*>(nullptr), int64_t(0), int64_t(0), int64_t(0), int64_t(0));
 }
 }  // namespace
@@ -1179,6 +1277,13 @@ void launch_apply_field(const KParams& k, const void* g, bool f32, int64_t si, i
                         hipStream_t s) {
   const float* gf = static_cast<const float*>(g);
   const double* gd = static_cast<const double*>(g);
+  if (fielded(k)) {
+    if (f32 && resid) apply_field_launch<float, true, false, true>(k, gf, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
+    else if (f32) apply_field_launch<float, false, false, true>(k, gf, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
+    else if (resid) apply_field_launch<double, true, false, true>(k, gd, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
+    else apply_field_launch<double, false, false, true>(k, gd, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
+    return;
+  }
   if (shifted(k)) {
     if (f32 && resid) apply_field_launch<float, true, true>(k, gf, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
     else if (f32) apply_field_launch<float, false, true>(k, gf, si, sj, rhs, dst, dsi, dsj, off_i, off_j, s);
@@ -1207,12 +1312,14 @@ void launch_group_reduce(double* const* bufs, int nranks, int n, int is_max, hip
 }
 
 void launch_apply_A(const KParams& k, const double* p, double* Ap, hipStream_t s) {
-  if (shifted(k)) hipLaunchKernelGGL((kApplyA<false, true>), dim3(flat_blocks(k)), dim3(TJ), 0, s, k, p, Ap);
+  if (fielded(k)) hipLaunchKernelGGL((kApplyA<false, false, true>), dim3(flat_blocks(k)), dim3(TJ), 0, s, k, p, Ap);
+  else if (shifted(k)) hipLaunchKernelGGL((kApplyA<false, true>), dim3(flat_blocks(k)), dim3(TJ), 0, s, k, p, Ap);
   else hipLaunchKernelGGL(kApplyA<false>, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, p, Ap);
 }
 
 void launch_coef(const KParams& k, double* a, double* b, double* D, hipStream_t s) {
-  if (shifted(k)) hipLaunchKernelGGL(kCoef<true>, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, a, b, D);
+  if (fielded(k)) hipLaunchKernelGGL((kCoef<false, true>), dim3(flat_blocks(k)), dim3(TJ), 0, s, k, a, b, D);
+  else if (shifted(k)) hipLaunchKernelGGL(kCoef<true>, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, a, b, D);
   else hipLaunchKernelGGL(kCoef<false>, dim3(flat_blocks(k)), dim3(TJ), 0, s, k, a, b, D);
 }
 

@@ -256,8 +256,14 @@ struct KParams {
   // iteration, sqrt(g) ≤ st->red_G[1], instead of the step size after it (kF,
   // kS / kRed through sweep_term, kResident; the multi-step sweeps never run
   // under it).  0: the step-size rule, today's code.
-  // Last member: every other kernarg offset stays where it was.
   int stop_res;
+  // Problem::reaction: local (0, 0) of the reaction plane c of A + diag(c) —
+  // the classic p planes' pitch and column origin, the block with a one-node
+  // ring (rows 0 .. nx+1, columns 0 .. ny+1: the neighbours' values, 0 on the
+  // box boundary), zero padding beyond.  Non-null: the launch wrappers of
+  // kernels.hip pick their FIELD instantiations.  Null: today's code.
+  // Last member: every other kernarg offset stays where it was.
+  const double* creact;
 };
 // KParams::mlimit of the three-step replay launch (DevState::fixj)
 constexpr int kReplay3 = -2;
@@ -318,6 +324,8 @@ void launch_init_field(const KParams& k, const double* rhs, const double* w0, in
 // ≥ 0, float64 or (f32) float32.  The device twin of pe::block_field.
 void launch_slice_field(const void* g, bool f32, int64_t si, int64_t sj, int64_t gnx, int64_t gny, int64_t i0,
                         int64_t j0, int64_t nx, int64_t ny, int ring, double* out, hipStream_t s);
+// kRingToPitched: a dense (nx+2) × (ny+2) ring plane → dst + li·pitch + lj (the reaction plane, KParams::creact).
+void launch_ring_to_pitched(const double* ring, int64_t nx, int64_t ny, double* dst, int64_t pitch, hipStream_t s);
 // kGatherW: the owned w → dst[(off_i + li) si + (off_j + lj) sj], li < nx, lj < ny (after the w flush).
 void launch_gather_w(const KParams& k, double* dst, int64_t si, int64_t sj, int64_t off_i, int64_t off_j,
                      hipStream_t s);
@@ -420,8 +428,8 @@ void launch_S3(const KParams& k, int par, hipStream_t s);
 int resident_blocks_S3();
 constexpr int sweep_sums(int steps) { return steps >= 3 ? kNS3 : steps == 2 ? kNS2 : 7; }
 // (k.ti / k.order select the kernel variant: set them first)
-// (shift: the SHIFT instantiations of kF / kG — Problem::shift ≠ 0)
-int resident_blocks_classic(int variant, bool shift = false);
+// (shift: the SHIFT instantiations of kF / kG — Problem::shift ≠ 0; field: the FIELD ones — Problem::reaction)
+int resident_blocks_classic(int variant, bool shift = false, bool field = false);
 
 }  // namespace dev
 }  // namespace pe

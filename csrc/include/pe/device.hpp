@@ -186,6 +186,22 @@ class DeviceSolver {
   // resumed solve takes it again, as it takes rhs again.
   void set_exact(const double* owned);
   void set_exact_device(const void* g, int64_t si, int64_t sj, bool f32, hipStream_t producer);
+  // The reaction field c of A + diag(c) (pe/fields.hpp; a solver constructed
+  // with Problem::reaction, else std::invalid_argument): `ringed` (nx+2) ×
+  // (ny+2) (block_field ring 1 — kF forms p on the halo ring, so D + c is
+  // needed one node beyond the owned block; every rank holds the global array:
+  // no halo exchange) in host memory, or the global array in device memory,
+  // with set_rhs / set_rhs_device's stream and event ordering and pointer
+  // checks.  It is copied into a plane of the p planes' layout
+  // (KParams::creact) on the solver stream, takes effect at the next reset() /
+  // solve() / operator pass, and may be called again between solves (a Newton
+  // loop).  The values are the caller's to check (finite, ≥ 0:
+  // check_reaction).  Such a solver refuses reset() until a field is set; a
+  // null pointer is refused.  Not checkpointed: a resumed solve needs the same
+  // field again, as it needs rhs.
+  void set_reaction(const double* ringed);
+  void set_reaction_device(const void* g, int64_t si, int64_t sj, bool f32, hipStream_t producer);
+  bool user_reaction() const { return react_set_; }
   // Host copy of the user plane (0: rhs, nx × ny; 1: w0, (nx+2) × (ny+2);
   // 2: exact, nx × ny); empty when the field is unset.  Synchronizes the
   // stream (tests).
@@ -499,6 +515,12 @@ class DeviceSolver {
   double* halo_ = nullptr;    // send_dn, send_up, recv_dn, recv_up (nx each; ×4 single-sweep)
   int64_t hsize_ = 0;
   double* rhs_dev_ = nullptr;  // user right-hand side, dense nx × ny (null: F)
+  // reaction field: the dense ring plane set_plane / set_plane_device fill, and the plane of the p planes' layout
+  // the kernels read (KParams::creact = react_dev_ + blk_.base); allocated at construction under Problem::reaction
+  double* react_ring_ = nullptr;
+  double* react_dev_ = nullptr;
+  bool react_set_ = false;
+  void place_reaction();
   double* w0_dev_ = nullptr;   // user initial guess, dense (nx+2) × (ny+2) with its ring (null: opt_.init)
   double* exact_dev_ = nullptr;  // user exact solution, dense nx × ny (null: the analytic u)
   int device_ = 0;             // the device the solver was constructed on (device fields must live there)
@@ -605,6 +627,9 @@ struct DeviceFields {
   const void* exact = nullptr;
   int64_t exact_si = 0, exact_sj = 0;
   bool exact_f32 = false;
+  const void* reaction = nullptr;  // (with Problem::reaction; else UserFields::reaction)
+  int64_t reaction_si = 0, reaction_sj = 0;
+  bool reaction_f32 = false;
   double* w_dst = nullptr;    // (M-1) × (N-1), strides in elements
   int64_t w_si = 0, w_sj = 0;
   // destinations of the gradient (both or neither), (M-1) × (N-1) each with the same strides
@@ -635,6 +660,11 @@ struct OperatorFields {
   const void* rhs = nullptr;
   int64_t rhs_si = 0, rhs_sj = 0;
   bool rhs_f32 = false;
+  // the reaction field of A + diag(c) (with Problem::reaction), host or device
+  const double* reaction_host = nullptr;
+  const void* reaction = nullptr;
+  int64_t reaction_si = 0, reaction_sj = 0;
+  bool reaction_f32 = false;
   double* dst = nullptr;
   int64_t dst_si = 0, dst_sj = 0;
   std::vector<double>* host = nullptr;

@@ -14,6 +14,18 @@
 //        sqrt(h1 h2 Σ_D (w − exact)²) and max_err = max_D |w − exact| over the
 //        nodes inside the ellipse (values outside are ignored).  It takes the
 //        place of the built-in analytic solution and never enters the solve.
+//   reaction: the coefficient c of −Δu + c(x, y)·u = f (Problem::reaction goes
+//        with it): the system is (A + diag(c)) w = B at every interior node of
+//        the box, inside and outside the ellipse; B and its mask, the stop
+//        rules, norms, cap and statuses are unchanged; the preconditioner is
+//        D + c.  Per node exactly the shifted trees below with c_ij for σ —
+//        shifted_apply(Ax + Ay, c_ij, p_ij) and shifted_diag(D_ij, c_ij) —
+//        at every node alike, c_ij = 0 included (Av + 0·p: no branch per
+//        node).  Finite and ≥ 0 everywhere (check_reaction); the built-in
+//        analytic solution does not apply (l2_err = max_err = −1 without
+//        `exact`).  The host paths read it at owned nodes (block_field ring
+//        0), the device kernels one node beyond (ring 1: kF forms p on the
+//        halo ring).
 // A null field keeps the built-in path (constant F / Init / the analytic
 // error, or -1 with a user rhs) bit for bit.
 #pragma once
@@ -30,6 +42,7 @@ struct UserFields {
   const double* rhs = nullptr;
   const double* w0 = nullptr;
   const double* exact = nullptr;
+  const double* reaction = nullptr;
 };
 
 // Block `blk`'s share of the global interior array `g` of an M × N grid,
@@ -74,7 +87,10 @@ GradStats gradient_field(const Problem& prob, const double* w, double* gx, doubl
 // system has unknowns everywhere).  Returns h1·h2·Σ v·(A v).  `out` may be
 // null: the sum only.  With prob.shift = σ > 0 both functions take A_σ (below)
 // for A: out = A_σ v and h1·h2·Σ v·(A_σ v), out = B − A_σ w and h1·h2·Σ out².
-double apply_operator(const Problem& prob, const double* v, double* out, int threads = 1);
+// `reaction` (with prob.reaction): the global interior array c of A + diag(c),
+// per node the same tree with c_ij for σ.
+double apply_operator(const Problem& prob, const double* v, double* out, int threads = 1,
+                      const double* reaction = nullptr);
 // The shifted operator A_σ = A + σI (Problem::shift = σ > 0; −Δu + σu = f) —
 // the two expression trees every backend uses, host and device:
 //   A_σ p = (Ax + Ay) + σ·p     the unshifted tree, then one multiply and one add;
@@ -89,6 +105,11 @@ PE_HD double shifted_diag(double D, double sigma) { return D + sigma; }
 // std::invalid_argument unless prob.shift is finite and ≥ 0 (a negative shift
 // makes the system indefinite).  Every backend calls it before any work.
 void check_shift(const Problem& prob, const char* who);
+// The reaction field `c` of `prob` (global interior array; UserFields::reaction).
+// std::invalid_argument unless prob.reaction and `c` go together (both or
+// neither), prob.shift == 0 with them ("add the constant to the field"), and
+// every entry is finite and ≥ 0.  Every backend calls it before any work.
+void check_reaction(const Problem& prob, const double* c, const char* who);
 // The breakdown test every backend makes before α = g / den exists, den =
 // h1·h2·(Ap, p), g = h1·h2·(z, r).  Step-size rule: the reference's absolute
 // |den| < 1e-15 (stage2-mpi/poisson_mpi_decomp.cpp:413), bit for bit.  Residual
@@ -111,6 +132,7 @@ inline double stop_threshold(const Problem& prob, double g0) {
 }
 // out = B − A w, B = rhs (null: F) at nodes inside the ellipse, 0 elsewhere
 // (assemble()'s mask).  Returns h1·h2·Σ out².  `out` may be null.
-double residual_field(const Problem& prob, const double* w, const double* rhs, double* out, int threads = 1);
+double residual_field(const Problem& prob, const double* w, const double* rhs, double* out, int threads = 1,
+                      const double* reaction = nullptr);
 
 }  // namespace pe

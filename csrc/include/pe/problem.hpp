@@ -52,6 +52,11 @@ struct Problem {
   // of its threshold (finite, ≥ 0; pe/fields.hpp check_stop).
   Stop stop = Stop::Step;
   double atol = 0.0;
+  // A per-node reaction coefficient c ≥ 0: (A + diag(c)) w = B, the discrete
+  // −Δu + c(x, y)·u = f.  The array travels with the solve's fields
+  // (pe/fields.hpp UserFields::reaction); this flag fixes the plan.  false:
+  // today's code bit for bit.
+  bool reaction = false;
 
   double h1() const { return (B1 - A1) / M; }
   double h2() const { return (B2 - A2) / N; }

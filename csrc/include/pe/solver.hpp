@@ -130,6 +130,10 @@ struct SolveResult {
 // prob.shift = σ > 0 solves (A + σI) w = B with the preconditioner D + σ
 // (pe/fields.hpp); the analytic error is then -1 too unless fields.exact is
 // given.  std::invalid_argument for a negative or non-finite shift.
+// fields.reaction = c (with prob.reaction) solves (A + diag(c)) w = B with the
+// preconditioner D + c, per node the same two expressions with c_ij for σ; the
+// analytic error is −1 as with a shift.  std::invalid_argument from
+// check_reaction (pe/fields.hpp) before any work.
 SolveResult cpu_pcg(const Problem& prob, const Block& blk, HostComm& comm,
                     const SolveOptions& opt, std::vector<double>* w_out = nullptr,
                     const UserFields& fields = UserFields());

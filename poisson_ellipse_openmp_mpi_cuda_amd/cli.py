@@ -55,8 +55,18 @@ launch (``--algo auto``, ``classic`` or ``fused``):
 
     python -m poisson_ellipse_openmp_mpi_cuda_amd.cli --stop residual --shift 40 --rhs f.npy --w0 u.npy --atol 1e-7 400 600
 
+``--reaction FILE.npy`` solves −Δu + c(x, y)·u = f, (A + diag(c)) w = B, with the
+per-node coefficient c >= 0 of the file, float64 (M-1, N-1) like ``--rhs`` — one
+Newton step of a semilinear problem, an absorption that differs between
+regions.  Not together with ``--shift`` (add the constant to the field); the
+error line reads ``n/a`` unless ``--exact`` is given, ``--json`` carries
+``"reaction": true``, and the device backends run ``--algo auto`` / ``classic``:
+
+    python -m poisson_ellipse_openmp_mpi_cuda_amd.cli --reaction c.npy --rhs f.npy --dump u.npy 400 600
+
 Checkpoints hold the iteration state, not the fields: ``--resume`` needs the
-same ``--rhs`` (and ``--exact``) and the same ``--shift`` again, and ignores ``--w0``.
+same ``--rhs`` (and ``--exact``), the same ``--shift`` and the same ``--reaction``
+again, and ignores ``--w0``.
 """
 
 from __future__ import annotations
@@ -69,7 +79,7 @@ import sys
 import numpy as np
 
 from .models.ellipse import PRESETS, EllipseProblem
-from .solver import BACKENDS, residual, solve, user_field
+from .solver import BACKENDS, reaction_problem, residual, solve, user_field
 from .utils import dump as _dump
 from .utils.report import json_report, legacy_lines
 
@@ -102,6 +112,10 @@ def build_parser():
                     help="constant shift S >= 0 of the operator: solve -Laplace(u) + S u = f, (A + S I) w = B (default 0: "
                          "the unshifted solve); the L2 / max error is then reported only with --exact; device backends "
                          "run --algo auto / classic; a resumed solve (--resume) needs the same --shift again")
+    ap.add_argument("--reaction", default=None, metavar="FILE.npy",
+                    help="per-node reaction coefficient c >= 0: float64 (M-1, N-1) array; solve -Laplace(u) + c u = f, "
+                         "(A + diag(c)) w = B; not together with --shift; the L2 / max error is then reported only with "
+                         "--exact; device backends run --algo auto / classic; a resumed solve needs it again")
     ap.add_argument("--tol", type=float, default=1e-6)
     ap.add_argument("--stop", choices=("step", "residual"), default="step",
                     help="stop rule: step (default) — the step size ||w_{k+1} - w_k|| < tol; residual — the "
@@ -153,22 +167,28 @@ def main(argv=None) -> int:
         rhs = None if a.rhs is None else user_field("--rhs", np.load(a.rhs, allow_pickle=False), prob)
         w0 = None if a.w0 is None else user_field("--w0", np.load(a.w0, allow_pickle=False), prob)
         exact = None if a.exact is None else user_field("--exact", np.load(a.exact, allow_pickle=False), prob)
+        reaction = None
+        if a.reaction is not None:
+            reaction = reaction_problem(prob, user_field("--reaction", np.load(a.reaction, allow_pickle=False), prob),
+                                        False, a.algo)[1]
     except (OSError, ValueError) as e:
         print(f"error: {e}", file=sys.stderr)
         return 2
     rep = solve(prob, backend=a.backend, ranks=a.ranks, threads=a.threads, decomp=a.decomp, init=a.init,
                 seed=a.seed, return_w=want_w, variant=a.variant, timing=a.timing, graph=a.graph and not a.no_graph,
                 algo=a.algo, checkpoint=a.checkpoint, checkpoint_every=a.checkpoint_every, resume=a.resume,
-                log_every=a.log_every, rhs=rhs, w0=w0, exact=exact,
+                log_every=a.log_every, rhs=rhs, w0=w0, exact=exact, reaction=reaction,
                 return_grad=True if a.dump_grad else "stats" if a.grad_stats else False)
     if rep.rank != 0:
         return 0
     if not a.quiet:
         print(legacy_lines(rep, a.tol))
-        if (rhs is None and prob.shift == 0.0) or exact is not None:
+        if (rhs is None and prob.shift == 0.0 and reaction is None) or exact is not None:
             err = f"L2 error in D ~ {rep.l2_err:.6e} | max error in D ~ {rep.max_err:.6e}"
         elif rhs is not None:
             err = "L2 error in D ~ n/a (user right-hand side)"
+        elif reaction is not None:
+            err = "L2 error in D ~ n/a (reaction field)"
         else:
             err = "L2 error in D ~ n/a (shifted operator)"
         print(f"   Process grid {rep.Px}x{rep.Py} | iters/s ~ {rep.iters_per_s:.1f} | {err}")
@@ -182,7 +202,7 @@ def main(argv=None) -> int:
 
         alone = a.backend not in ("hip", "dist-cpu") or env_rank_world()[1] == 1
         res = residual(prob, rep.w, rhs, backend=a.backend if alone else "omp", ranks=a.ranks, threads=a.threads,
-                       decomp=a.decomp)
+                       decomp=a.decomp, reaction=reaction)
         np.save(a.dump_resid, res.field)
         print(f"   Residual ||B - A w||_E ~ {math.sqrt(res.sum):.6e}")
     if a.json:

@@ -42,6 +42,10 @@ class EllipseProblem:
     stop: str = "step"
     # absolute floor of the residual rule's threshold (finite, >= 0; only with stop="residual")
     atol: float = 0.0
+    # a per-node reaction coefficient c >= 0 goes with the solve: (A + diag(c)) w = B, i.e. −Δu + c(x, y)·u = f.  The
+    # array itself is the solve's ``reaction=`` argument (solve() / DeviceSession set this flag from it); the flag fixes
+    # the plan — the classic device path.  False: today's code bit for bit.
+    reaction: bool = False
 
     # ---- derived quantities (same formulas as csrc/include/pe/problem.hpp)
     @property
@@ -118,6 +122,7 @@ class EllipseProblem:
         p.shift = shift
         p.stop = nat.Stop.Residual if res_rule else nat.Stop.Step
         p.atol = atol
+        p.reaction = bool(self.reaction)
         return p
 
 

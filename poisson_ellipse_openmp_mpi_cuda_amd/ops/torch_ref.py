@@ -109,32 +109,59 @@ def assemble(prob: EllipseProblem, device="cpu", *, rhs=None):
     return t(a), t(b), t(B)
 
 
-def apply_A(p, a, b, h1, h2, shift: float = 0.0):
+def _is_field(shift) -> bool:
+    return isinstance(shift, torch.Tensor)
+
+
+def reaction_coef(prob: EllipseProblem, reaction, device="cpu"):
+    """What apply_A / diag take for `shift`: prob.shift as a float, or — with a
+    reaction field c over the interior, shape (M-1, N-1) — c as an fp64 tensor
+    (pe/fields.hpp: the shifted trees with c_ij for σ at every node, zeros
+    included).  ValueError: a field together with a non-zero shift, a wrong
+    shape, a negative or non-finite entry."""
+    sigma = prob.check_shift()
+    if reaction is None:
+        return sigma
+    if sigma != 0.0:
+        raise ValueError(f"reaction together with shift != 0 (got {prob.shift}): add the constant to the field")
+    c = embed(prob, reaction, device)[1:-1, 1:-1].clone()
+    if not bool(torch.isfinite(c).all()) or not bool((c >= 0).all()):
+        raise ValueError("reaction must be finite and >= 0 at every node")
+    return c
+
+
+def apply_A(p, a, b, h1, h2, shift=0.0):
     """(A p) on interior nodes; boundary rows/cols of the result are 0.
     shift σ ≠ 0 (EllipseProblem.shift): A_σ p = (Ax + Ay) + σ·p, the tree of
-    csrc/include/pe/fields.hpp (one multiply, one add; 0 keeps Ax + Ay)."""
+    csrc/include/pe/fields.hpp (one multiply, one add; 0 keeps Ax + Ay).  A
+    tensor (reaction_coef: the reaction field c over the interior) takes σ's
+    place node by node, c_ij = 0 included."""
     out = torch.zeros_like(p)
     pc = p[1:-1, 1:-1]
     Ax = (-1.0 / h1) * (_div(a[2:, 1:-1] * (p[2:, 1:-1] - pc), h1) - _div(a[1:-1, 1:-1] * (pc - p[:-2, 1:-1]), h1))
     Ay = (-1.0 / h2) * (_div(b[1:-1, 2:] * (p[1:-1, 2:] - pc), h2) - _div(b[1:-1, 1:-1] * (pc - p[1:-1, :-2]), h2))
-    out[1:-1, 1:-1] = (Ax + Ay) + shift * pc if shift != 0.0 else Ax + Ay
+    if _is_field(shift):
+        out[1:-1, 1:-1] = (Ax + Ay) + shift * pc
+    else:
+        out[1:-1, 1:-1] = (Ax + Ay) + shift * pc if shift != 0.0 else Ax + Ay
     return out
 
 
-def residual(prob: EllipseProblem, W, rhs=None, device="cpu"):
+def residual(prob: EllipseProblem, W, rhs=None, device="cpu", *, reaction=None):
     """B − A W as an (M+1, N+1) tensor (0 on the box boundary): W an interior
     (M-1, N-1) array or a full tensor, B = rhs (None: F) inside the ellipse
     and 0 outside — the torch form of native.residual_field (A + σI with
-    prob.shift = σ)."""
+    prob.shift = σ, A + diag(c) with `reaction` = c)."""
     a, b, B = assemble(prob, device, rhs=rhs)
-    return B - apply_A(embed(prob, W, device), a, b, prob.h1, prob.h2, prob.check_shift())
+    return B - apply_A(embed(prob, W, device), a, b, prob.h1, prob.h2, reaction_coef(prob, reaction, device))
 
 
-def diag(a, b, h1, h2, shift: float = 0.0):
-    """Jacobi diagonal D on interior nodes (0 elsewhere); shift σ ≠ 0: D_σ = D + σ."""
+def diag(a, b, h1, h2, shift=0.0):
+    """Jacobi diagonal D on interior nodes (0 elsewhere); shift σ ≠ 0: D_σ = D + σ;
+    a tensor (the reaction field over the interior): D + c node by node."""
     D = torch.zeros_like(a)
     D[1:-1, 1:-1] = _div(a[2:, 1:-1] + a[1:-1, 1:-1], h1 * h1) + _div(b[1:-1, 2:] + b[1:-1, 1:-1], h2 * h2)
-    if shift != 0.0:
+    if _is_field(shift) or shift != 0.0:
         D[1:-1, 1:-1] = D[1:-1, 1:-1] + shift
     return D
 
@@ -184,18 +211,20 @@ def _start(prob, device, rhs, w0):
 
 
 def pcg(prob: EllipseProblem, device="cpu", w0=None, max_iter: Optional[int] = None,
-        keep_history: bool = False, *, rhs=None, exact=None) -> TorchPCGResult:
+        keep_history: bool = False, *, rhs=None, exact=None, reaction=None) -> TorchPCGResult:
     """Reference-algorithm Jacobi PCG (stage2 solve_mpi order of operations).
     l2_err / max_err: against the user's `exact` when given, else against the
     analytic solution; with a user rhs, or a shifted operator (prob.shift ≠ 0:
     (A + σI) w = B, preconditioner D + σ), and no `exact` there is nothing to
     compare with: -1.  prob.stop == "residual": iterate k is tested at the top
     of iteration k + 1, sqrt(g_k) <= max(tol·sqrt(g_0), atol) with g = h1·h2·(z, r),
-    instead of the step size after it (csrc/cpu/pcg_cpu.cpp, the same loop)."""
+    instead of the step size after it (csrc/cpu/pcg_cpu.cpp, the same loop).
+    `reaction`: the field c of (A + diag(c)) w = B, preconditioner D + c — where
+    the loop takes the scalar shift it takes c (reaction_coef); no analytic error."""
     res_rule, atol = prob.check_stop()
     a, b, B = assemble(prob, device, rhs=rhs)
     h1, h2 = prob.h1, prob.h2
-    sigma = prob.check_shift()
+    sigma = reaction_coef(prob, reaction, device)
     D = diag(a, b, h1, h2, sigma)
     w = torch.zeros_like(B) if w0 is None else embed(prob, w0, device)
     r = B - apply_A(w, a, b, h1, h2, sigma)
@@ -239,7 +268,7 @@ def pcg(prob: EllipseProblem, device="cpu", w0=None, max_iter: Optional[int] = N
     if exact is not None:
         l2, mx = error_vs_analytic(prob, w, embed(prob, exact, device))
     else:
-        l2, mx = error_vs_analytic(prob, w) if rhs is None and sigma == 0.0 else (-1.0, -1.0)
+        l2, mx = error_vs_analytic(prob, w) if rhs is None and not _is_field(sigma) and sigma == 0.0 else (-1.0, -1.0)
     return TorchPCGResult(k, converged, w, l2, mx, hist, nat0, nat, thr)
 
 
@@ -254,17 +283,18 @@ class ClassicState:
     w: torch.Tensor
 
 
-def classic(prob: EllipseProblem, iters: int, device="cpu", *, rhs=None, w0=None) -> ClassicState:
+def classic(prob: EllipseProblem, iters: int, device="cpu", *, rhs=None, w0=None, reaction=None) -> ClassicState:
     """The reference loop (pcg) without its stop test, for exactly `iters`
     iterations, with prob.shift: the state the classic two-kernel device path
     (csrc/hip/kernels.hip kF + kG) holds then.  Iteration k: p_k = z_{k-1} +
     β_k p_{k-1}, the sums Σ Ap_k·p_k and Σ p_k·p_k (DevState::red_F), α_k,
     w_k = w_{k-1} + α_k p_k, r_k = r_{k-1} − α_k A p_k, Σ z_k·r_k
     (DevState::red_G).  p is p_K — what kF stored last — not the p_{K+1} pcg
-    forms at the end of its loop; the sums are unweighted (no h1 h2)."""
+    forms at the end of its loop; the sums are unweighted (no h1 h2).
+    `reaction`: the field c in the shift's place, as in pcg."""
     a, b, B = assemble(prob, device, rhs=rhs)
     h1, h2 = prob.h1, prob.h2
-    sigma = prob.check_shift()
+    sigma = reaction_coef(prob, reaction, device)
     D = diag(a, b, h1, h2, sigma)
     inner = lambda u, v: float((u[1:-1, 1:-1] * v[1:-1, 1:-1]).sum())  # noqa: E731  (unweighted)
     w = torch.zeros_like(B) if w0 is None else embed(prob, w0, device)

@@ -18,6 +18,7 @@ stage4-mpi+cuda/poisson_mpi_cuda2.cu:986-1036) and its transports:
 
 from __future__ import annotations
 
+import atexit
 import datetime
 import os
 from dataclasses import dataclass
@@ -67,7 +68,24 @@ def init(backend: Optional[str] = None, timeout_s: float = 300.0) -> DistContext
     if torch.cuda.is_available() and "nccl" in backend:
         torch.cuda.set_device(local % max(1, torch.cuda.device_count()))
     dist.init_process_group(**kw)
+    # A rank process that ends with its process group alive races the
+    # interpreter's teardown against the group's worker threads: a joinable
+    # std::thread destroyed at exit is std::terminate ("terminate called
+    # without an active exception", SIGABRT — seen on busy machines in one rank
+    # of three after its solve had finished and its result was written, on CPU
+    # ranks and on GPU ranks alike).  Destroy the group while the interpreter
+    # is whole, as torch asks ("destroy_process_group() was not called before
+    # program exit").  The native communicators do not depend on it.
+    atexit.register(_destroy_at_exit)
     return DistContext(rank, world, local, backend, True)
+
+
+def _destroy_at_exit():
+    try:
+        if dist.is_available() and dist.is_initialized():
+            dist.destroy_process_group()
+    except Exception:  # (a peer that is already gone: nothing left to tidy)
+        pass
 
 
 def shutdown(ctx: DistContext):

@@ -100,6 +100,8 @@ class SolveReport:
     res_nat0: float = -1.0
     res_nat: float = -1.0
     stop_thr: float = -1.0
+    # the solve had a reaction field (to_dict() / --json carry "reaction": true only then)
+    reaction: bool = False
 
     @property
     def iters_per_s(self) -> float:
@@ -114,6 +116,8 @@ class SolveReport:
         d["iters_per_s"] = self.iters_per_s
         if not d.get("shift"):
             d.pop("shift", None)
+        if not d.get("reaction"):
+            d.pop("reaction", None)
         if d.get("stop") == "step":
             for key in ("stop", "atol", "res_nat0", "res_nat", "stop_thr"):
                 d.pop(key, None)
@@ -228,6 +232,41 @@ def _field_arg(name, f, prob, on_device: bool):
     return user_field(name, f, prob)
 
 
+def reaction_problem(prob: EllipseProblem, reaction, on_device: bool, algo="auto"):
+    """(problem, field) of a call with ``reaction=``: the field checked — shape
+    and dtype as ``rhs`` (a host array, or on the hip backends a GPU tensor,
+    float64 / float32, any strides), every entry finite and >= 0 (on a GPU tensor
+    with torch.isfinite / (c >= 0).all(), before any launch) — and the problem
+    with its ``reaction`` flag set.  ValueError also for a field together with
+    ``shift != 0`` and with ``algo`` fused / two-step / three-step, and for a
+    problem flagged ``reaction`` without a field.  None with an unflagged
+    problem passes through: today's call."""
+    if reaction is None:
+        if prob.reaction:
+            raise ValueError("reaction: the problem has reaction=True but no field was given (pass reaction=c)")
+        return prob, None
+    if prob.check_shift() != 0.0:
+        raise ValueError(f"reaction together with shift != 0 (got {prob.shift}): add the constant to the field")
+    name = algo if isinstance(algo, str) else {v: k for k, v in ALGOS.items()}.get(int(algo), str(algo))
+    if name in ("fused", "two-step", "three-step"):
+        raise ValueError(f'algo "{name}": the single-sweep kernels carry no reaction field; a solve with reaction runs '
+                         'algo "auto" or "classic"')
+    c = _field_arg("reaction", reaction, prob, on_device)
+    if is_device_tensor(c):
+        import torch
+
+        t = c.detach()
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError("reaction: non-finite values")
+        if not bool((t >= 0).all()):
+            raise ValueError("reaction: negative values (the field must be >= 0 at every node: a negative coefficient "
+                             "can make the system indefinite)")
+    elif not bool((c >= 0.0).all()):
+        raise ValueError("reaction: negative values (the field must be >= 0 at every node: a negative coefficient can "
+                         "make the system indefinite)")
+    return (prob if prob.reaction else dataclasses.replace(prob, reaction=True)), c
+
+
 def _stream_handle(index: int) -> int:
     import torch
 
@@ -248,7 +287,7 @@ def _report(backend, prob, res, ranks, threads, init, w=None, rank=0) -> SolveRe
         b_norm=float(getattr(res, "b_norm", -1.0)), restarts=int(getattr(res, "restarts", 0)),
         shift=float(prob.shift), stop=str(prob.stop), atol=float(prob.atol),
         res_nat0=float(getattr(res, "res_nat0", -1.0)), res_nat=float(getattr(res, "res_nat", -1.0)),
-        stop_thr=float(getattr(res, "stop_thr", -1.0)))
+        stop_thr=float(getattr(res, "stop_thr", -1.0)), reaction=bool(prob.reaction))
 
 
 def _grad_mode(return_grad, on_device: bool, backend: str = "hip"):
@@ -276,7 +315,7 @@ def _host_gradient(rep: SolveReport, prob: EllipseProblem, w, mode) -> SolveRepo
 
 def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: int = 1, decomp: str | None = None,
           init: str = "zero", seed: int = 1234, return_w: bool | str = False, device: str = "cuda", rhs=None,
-          w0=None, exact=None, return_grad: bool | str = False, **kw) -> SolveReport:
+          w0=None, exact=None, return_grad: bool | str = False, reaction=None, **kw) -> SolveReport:
     """Solve the fictitious-domain Poisson problem with the chosen backend.
 
     ``rhs`` / ``w0`` (every backend): a user right-hand side and initial guess
@@ -300,6 +339,18 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
     ValueError).  A resumed solve needs the same shift again: checkpoints do
     not hold it.  σ must be finite and ≥ 0 (ValueError); 0 is today's solve
     bit for bit.
+
+    ``reaction`` = c (every backend): a per-node coefficient c >= 0 over the
+    global interior, in the forms ``rhs`` takes — (A + diag(c)) w = B, the
+    discrete −Δu + c(x, y)·u = f, at every interior node of the box, with the
+    preconditioner D + c: per node the shift's expressions with c_ij for σ
+    (csrc/include/pe/fields.hpp), zeros included.  B, the stop rules, norms
+    and statuses are unchanged; ``l2_err`` / ``max_err`` are −1 unless
+    ``exact`` is given.  The device backends run the classic two-kernel path.
+    ValueError before any work: a negative or non-finite entry, a wrong shape
+    or dtype, a field together with ``shift != 0`` (add the constant to the
+    field), ``algo`` fused / two-step / three-step.  A resumed solve needs the
+    same field again.  None: today's solve bit for bit.
 
     ``prob.stop`` = "residual" (every backend) stops on the preconditioned
     residual instead of the step size: with g_k = h1·h2·Σ z_k·r_k, z = D⁻¹r —
@@ -367,6 +418,7 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
     rhs = _field_arg("rhs", rhs, prob, on_device)
     w0 = _field_arg("w0", w0, prob, on_device)
     exact = _field_arg("exact", exact, prob, on_device)
+    prob, reaction = reaction_problem(prob, reaction, on_device, kw.get("algo", "auto"))
     if w0 is not None:
         init = "field"
     decomp = decomp or _decomp.default_spec(backend)
@@ -377,7 +429,7 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
         nranks = ranks if backend == "ranks" else 1
         opt = _options(init, seed, t, keep_history=kw.get("keep_history", False), log_every=kw.get("log_every", 0))
         res, w = nat.cpu_solve_grid(P, _decomp.grid(nranks, prob.M, prob.N, decomp if backend == "ranks" else "reference"),
-                                    opt, bool(return_w or grad), rhs, w0, exact)
+                                    opt, bool(return_w or grad), rhs, w0, exact, reaction)
         rep = _report(backend, prob, res, nranks, t, init, np.asarray(w) if return_w else None)
         return _host_gradient(rep, prob, w, grad) if grad else rep
     if backend == "torch":
@@ -389,7 +441,7 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
             device = "cpu"
         t0 = time.perf_counter()
         r = torch_ref.pcg(prob, device=device, w0=w0, keep_history=kw.get("keep_history", False), rhs=rhs,
-                          exact=exact)
+                          exact=exact, reaction=reaction)
         dt = time.perf_counter() - t0
         timers = dict(solver=dt, iterate=dt)
         rep = SolveReport("torch", prob.M, prob.N, 1, 1, 1, 1, r.iters, r.converged, False,
@@ -397,7 +449,7 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
                           "zero" if w0 is None else "field",
                           r.w[1:-1, 1:-1].cpu().numpy() if return_w else None, shift=float(prob.shift),
                           stop=str(prob.stop), atol=float(prob.atol), res_nat0=r.res_nat0, res_nat=r.res_nat,
-                          stop_thr=r.stop_thr)
+                          stop_thr=r.stop_thr, reaction=bool(prob.reaction))
         if grad:
             g, *stats = torch_ref.gradient(prob, r.w)
             _set_grad(rep, stats, g.cpu().numpy() if grad is True else None)
@@ -408,13 +460,13 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
                        algo=kw.get("algo", "auto"))
         pg = _decomp.grid(ranks, prob.M, prob.N, decomp)
         if not (is_device_tensor(rhs) or is_device_tensor(w0) or is_device_tensor(exact) or return_w == "device"
-                or grad):
-            res, w = nat.device_solve_group_grid(P, pg, opt, return_w, rhs, w0, exact)
+                or grad or is_device_tensor(reaction)):
+            res, w = nat.device_solve_group_grid(P, pg, opt, return_w, rhs, w0, exact, reaction)
             return _report(backend, prob, res, ranks, 1, init, None if w is None else np.asarray(w))
         import torch
 
         index = nat.current_device()  # the virtual ranks run on the process's current device
-        fields = (("rhs", rhs), ("w0", w0), ("exact", exact))
+        fields = (("rhs", rhs), ("w0", w0), ("exact", exact), ("reaction", reaction))
         dev = {n: device_field(n, f, prob, index) for n, f in fields if is_device_tensor(f)}
         host = {n: f for n, f in fields if n not in dev}
         wt = w_dev = None
@@ -424,7 +476,8 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
         if not grad:
             res, w = nat.device_solve_group_grid_device(P, pg, opt, bool(return_w) and wt is None, host.get("rhs"),
                                                         host.get("w0"), dev.get("rhs"), dev.get("w0"), w_dev,
-                                                        _stream_handle(index), host.get("exact"), dev.get("exact"))
+                                                        _stream_handle(index), host.get("exact"), dev.get("exact"),
+                                                        host.get("reaction"), dev.get("reaction"))
             if wt is None and w is not None:
                 wt = np.asarray(w)
             return _report(backend, prob, res, ranks, 1, init, wt)
@@ -434,7 +487,8 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
             g_dev = (gt[0].data_ptr(), gt[1].data_ptr(), gt.stride(1), gt.stride(2))
         res, w, g = nat.device_solve_group_grad(P, pg, opt, bool(return_w) and wt is None, 1 if grad == "stats" else 2,
                                                 host.get("rhs"), host.get("w0"), host.get("exact"), dev.get("rhs"),
-                                                dev.get("w0"), dev.get("exact"), w_dev, g_dev, _stream_handle(index))
+                                                dev.get("w0"), dev.get("exact"), w_dev, g_dev, _stream_handle(index),
+                                                host.get("reaction"), dev.get("reaction"))
         if wt is None and w is not None:
             wt = np.asarray(w)
         if gt is None and g is not None:
@@ -444,16 +498,16 @@ def solve(prob: EllipseProblem, backend: str = "hip", ranks: int = 1, threads: i
     from .parallel import dist as _dist
 
     if backend == "dist-cpu":
-        ctx = _dist.init()
+        ctx = _dist.init("gloo")  # (CPU ranks need no device side; a gloo-only group is destroyed at exit)
         blk = _decomp.block(prob.M, prob.N, ctx.world, ctx.rank, decomp)
         opt = _options(init, seed, max(1, threads))
-        res, w = nat.cpu_solve_rank(P, blk, *_dist.gloo_callbacks(), opt, True, rhs, w0, exact)
+        res, w = nat.cpu_solve_rank(P, blk, *_dist.gloo_callbacks(), opt, True, rhs, w0, exact, reaction)
         wg = _dist.gather_blocks(ctx, prob, blk, np.asarray(w)) if return_w or grad else None
         rep = _report(backend, prob, res, ctx.world, threads, init, wg if return_w else None, ctx.rank)
         # (the gathered w lives on rank 0: its report carries the gradient and the figures)
         return _host_gradient(rep, prob, wg, grad) if grad and wg is not None else rep
     # hip
-    with DeviceSession(prob, decomp, init=init, seed=seed, **kw) as session:
+    with DeviceSession(prob, decomp, init=init, seed=seed, reaction=reaction, **kw) as session:
         return session._solve(rhs, w0, return_w, exact, grad)
 
 
@@ -465,7 +519,7 @@ def _out_mode(out, on_device: bool, backend: str = "hip") -> str:
     return out
 
 
-def _operator(prob, v, rhs, residual_, backend, ranks, threads, decomp, out, device, kw) -> FieldResult:
+def _operator(prob, v, rhs, residual_, backend, ranks, threads, decomp, out, device, kw, reaction=None) -> FieldResult:
     """apply_operator() / residual() on every backend."""
     name = "w" if residual_ else "v"
     if backend not in BACKENDS:
@@ -476,18 +530,20 @@ def _operator(prob, v, rhs, residual_, backend, ranks, threads, decomp, out, dev
         raise ValueError(f"{name}: a field is required")
     v = _field_arg(name, v, prob, on_device)
     rhs = _field_arg("rhs", rhs, prob, on_device) if residual_ else None
+    prob, reaction = reaction_problem(prob, reaction, on_device, kw.get("algo", "auto"))
     nat = native()
     P = prob.to_native()
     want = out != "sum"
     if backend in ("serial", "omp", "ranks", "dist-cpu"):
         # the host definition on the global array (every rank of a dist-cpu job holds it: no communication)
         t = 1 if backend == "serial" else max(1, threads)
-        s, f = nat.residual_field(P, v, rhs, want, t) if residual_ else nat.apply_operator(P, v, want, t)
+        s, f = (nat.residual_field(P, v, rhs, want, t, reaction) if residual_
+                else nat.apply_operator(P, v, want, t, reaction))
         rank = 0
         if backend == "dist-cpu":
             from .parallel import dist as _dist
 
-            rank = _dist.init().rank
+            rank = _dist.init("gloo").rank
         return FieldResult(np.asarray(f) if want and rank == 0 else None, float(s))
     if backend == "torch":
         import torch
@@ -498,11 +554,11 @@ def _operator(prob, v, rhs, residual_, backend, ranks, threads, decomp, out, dev
             device = "cpu"
         V = torch_ref.embed(prob, v, device)
         if residual_:
-            f = torch_ref.residual(prob, V, rhs, device)[1:-1, 1:-1]
+            f = torch_ref.residual(prob, V, rhs, device, reaction=reaction)[1:-1, 1:-1]
             s = float((f * f).sum())
         else:
             a, b, _ = torch_ref.assemble(prob, device)
-            f = torch_ref.apply_A(V, a, b, prob.h1, prob.h2, prob.shift)[1:-1, 1:-1]
+            f = torch_ref.apply_A(V, a, b, prob.h1, prob.h2, torch_ref.reaction_coef(prob, reaction, device))[1:-1, 1:-1]
             s = float((V[1:-1, 1:-1] * f).sum())
         return FieldResult(f.cpu().numpy() if want else None, prob.h1 * prob.h2 * s)
     if backend == "hip-group":
@@ -511,7 +567,7 @@ def _operator(prob, v, rhs, residual_, backend, ranks, threads, decomp, out, dev
         opt = _options(chunk=kw.get("chunk", 0), variant=kw.get("variant", 0), algo=kw.get("algo", "auto"))
         pg = _decomp.grid(ranks, prob.M, prob.N, decomp or _decomp.default_spec(backend))
         index = nat.current_device()
-        fields = ((name, v), ("rhs", rhs))
+        fields = ((name, v), ("rhs", rhs), ("reaction", reaction))
         dev = {n: device_field(n, f, prob, index) for n, f in fields if is_device_tensor(f)}
         host = {n: f for n, f in fields if n not in dev}
         ot = o_dev = None
@@ -519,9 +575,10 @@ def _operator(prob, v, rhs, residual_, backend, ranks, threads, decomp, out, dev
             ot = torch.empty((prob.M - 1, prob.N - 1), dtype=torch.float64, device=f"cuda:{index}")
             o_dev = (ot.data_ptr(), ot.stride(0), ot.stride(1))
         s, f = nat.device_apply_group(P, pg, opt, residual_, host.get(name), dev.get(name), host.get("rhs"),
-                                      dev.get("rhs"), o_dev, out == "host", _stream_handle(index))
+                                      dev.get("rhs"), o_dev, out == "host", _stream_handle(index), host.get("reaction"),
+                                      dev.get("reaction"))
         return FieldResult(ot if ot is not None else (np.asarray(f) if f is not None else None), float(s))
-    with DeviceSession(prob, decomp, **kw) as session:
+    with DeviceSession(prob, decomp, reaction=reaction, **kw) as session:
         return session._operator(v, rhs, residual_, out, set_rhs=True)
 
 
@@ -543,9 +600,17 @@ class DeviceSession:
     ``algo``, ``check_tol``, ``graph``, ``chunk``, ...).  The construction time
     is reported by the first solve only (``timers["construct"]`` is 0 after).
     On a multi-process job every rank creates the session and calls solve()
-    with the same global fields, as with ``solve()``."""
+    with the same global fields, as with ``solve()``.
 
-    def __init__(self, prob: EllipseProblem, decomp: str | None = None, **options):
+    ``reaction=c`` (a host array or a GPU tensor, as in solve()) makes it a
+    session of −Δu + c·u = f: the layout is fixed at construction, and
+    ``solve(..., reaction=c2)`` replaces the field per call — a Newton loop
+    passes its c = g′(u) there; left out, the last field stays.  ValueError for
+    ``reaction=`` on a session constructed without one, and for None on one
+    constructed with it."""
+
+    def __init__(self, prob: EllipseProblem, decomp: str | None = None, reaction=None, **options):
+        prob, reaction = reaction_problem(prob, reaction, True, options.get("algo", "auto"))  # (refusals before any work)
         nat = native()
         if nat.device_count() < 1:
             raise RuntimeError("backend 'hip' needs a visible MI355X (HIP device)")
@@ -572,6 +637,31 @@ class DeviceSession:
             self.block = _decomp.block(prob.M, prob.N, self.world, self.rank, decomp)
         self.device_index = int(nat.current_device())  # device tensors must live here
         self.solver = nat.DeviceSolver(prob.to_native(), self.block, self.comm, opt)
+        if reaction is not None:
+            self._set_reaction(reaction)
+
+    def _set_reaction(self, c) -> None:
+        """A checked field (reaction_problem) into the solver's reaction plane."""
+        if is_device_tensor(c):
+            self.solver.set_reaction_device(*device_field("reaction", c, self.prob, self.device_index),
+                                            _stream_handle(self.device_index))
+        else:
+            self.solver.set_reaction(native().block_field(self.prob.M, self.prob.N, self.block, c, 1))
+
+    def _reaction_arg(self, reaction):
+        """solve(reaction=)'s argument on this session: _KEEP passes, a field is checked; ValueError for a field on a
+        session constructed without one and for None on one constructed with it."""
+        if reaction is DeviceSession._KEEP:
+            return reaction
+        if not self.prob.reaction:
+            if reaction is None:
+                return DeviceSession._KEEP
+            raise ValueError("reaction: this session was constructed without a reaction field (the layout is fixed at "
+                             "construction: DeviceSession(prob, reaction=c))")
+        if reaction is None:
+            raise ValueError("reaction: None on a session constructed with a reaction field (pass a field, or leave it "
+                             "out to keep the last one)")
+        return reaction_problem(self.prob, reaction, True)[1]
 
     def close(self) -> None:
         """Release the solver (its device memory and stream); idempotent."""
@@ -584,7 +674,10 @@ class DeviceSession:
         self.close()
         return False
 
-    def solve(self, rhs=None, w0=None, exact=None, return_w=False, return_grad=False, atol=None) -> SolveReport:
+    _KEEP = object()
+
+    def solve(self, rhs=None, w0=None, exact=None, return_w=False, return_grad=False, atol=None,
+              reaction=_KEEP) -> SolveReport:
         """One solve on the kept solver.  ``rhs`` / ``w0`` / ``exact``: host
         arrays or GPU tensors of the global interior, per call and mixed
         freely; None clears a field back to F / ``init`` / the analytic error.  ``return_w``: False, True (numpy; on a
@@ -594,9 +687,12 @@ class DeviceSession:
         "stats", True or "device", as in solve().  ``atol`` (``stop="residual"``
         only): the absolute floor of the threshold from this solve on — the
         session's problem takes it; the kept solver, and any graph it has
-        captured, stay as they are (the threshold lives in device memory)."""
+        captured, stay as they are (the threshold lives in device memory).
+        ``reaction`` (a session constructed with one): the field of this and
+        the following solves; left out, the last one stays."""
         if isinstance(return_w, str) and return_w != "device":
             raise ValueError('return_w must be True, False or "device"')
+        reaction = self._reaction_arg(reaction)
         if atol is not None:
             prob = dataclasses.replace(self.prob, atol=atol)
             prob.check_stop()  # (ValueError before anything is set)
@@ -605,8 +701,12 @@ class DeviceSession:
             self.solver.set_atol(float(atol))
             self.prob = prob
         grad = _grad_mode(return_grad, True)
-        return self._solve(_field_arg("rhs", rhs, self.prob, True), _field_arg("w0", w0, self.prob, True), return_w,
-                           _field_arg("exact", exact, self.prob, True), grad)
+        rhs, w0, exact = (_field_arg(n, f, self.prob, True) for n, f in (("rhs", rhs), ("w0", w0), ("exact", exact)))
+        if reaction is not DeviceSession._KEEP:
+            if self.solver is None:
+                raise RuntimeError("DeviceSession is closed")
+            self._set_reaction(reaction)
+        return self._solve(rhs, w0, return_w, exact, grad)
 
     def apply(self, v, out="host") -> FieldResult:
         """A v for a field of the caller's on the kept solver.  ``v``: a host array
@@ -618,8 +718,6 @@ class DeviceSession:
         ``sum`` is h1·h2·Σ v·(A v).  The pass reads the solver's tables only: the
         next solve is the same solve."""
         return self._operator(_field_arg("v", v, self.prob, True), None, False, _out_mode(out, True))
-
-    _KEEP = object()
 
     def residual(self, w, rhs=_KEEP, out="host") -> FieldResult:
         """B − A w for an iterate of the caller's; ``sum`` is ‖B − A w‖²_E.
@@ -778,7 +876,8 @@ class DeviceSession:
 
 
 def apply_operator(prob: EllipseProblem, v, backend: str = "hip", ranks: int = 1, threads: int = 1,
-                   decomp: str | None = None, out: str = "host", device: str = "cuda", **kw) -> FieldResult:
+                   decomp: str | None = None, out: str = "host", device: str = "cuda", reaction=None,
+                   **kw) -> FieldResult:
     """A v: the fictitious-domain operator (coefficients and expression of the
     solve) applied to a field of the caller's.  ``v``: the global interior,
     shape (M-1, N-1), 0 on the box boundary — a host array on every backend, or
@@ -788,13 +887,15 @@ def apply_operator(prob: EllipseProblem, v, backend: str = "hip", ranks: int = 1
     written by the kernel) or "sum" (no field); the result's ``sum`` is
     h1·h2·Σ v·(A v).  Every backend gives the definition of
     csrc/include/pe/fields.hpp; DeviceSession.apply() serves a sequence of
-    calls from one constructed solver."""
-    return _operator(prob, v, None, False, backend, ranks, threads, decomp, out, device, kw)
+    calls from one constructed solver.  ``reaction`` = c: (A + diag(c)) v, the
+    field as in solve()."""
+    return _operator(prob, v, None, False, backend, ranks, threads, decomp, out, device, kw, reaction)
 
 
 def residual(prob: EllipseProblem, w, rhs=None, backend: str = "hip", ranks: int = 1, threads: int = 1,
-             decomp: str | None = None, out: str = "host", device: str = "cuda", **kw) -> FieldResult:
+             decomp: str | None = None, out: str = "host", device: str = "cuda", reaction=None, **kw) -> FieldResult:
     """B − A w for an iterate of the caller's: B = ``rhs`` (None: F) inside the
     ellipse and 0 outside, as solve() masks it.  ``sum`` is h1·h2·Σ (B − A w)²,
-    the square of the E-norm of the residual.  Arguments as apply_operator()."""
-    return _operator(prob, w, rhs, True, backend, ranks, threads, decomp, out, device, kw)
+    the square of the E-norm of the residual.  Arguments as apply_operator()
+    (``reaction`` = c: B − (A + diag(c)) w)."""
+    return _operator(prob, w, rhs, True, backend, ranks, threads, decomp, out, device, kw, reaction)
